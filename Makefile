@@ -84,8 +84,9 @@ $(CLI): $(HOST_SRCS) $(HOST_HDRS) $(LIB) include/stencil_hip.h
 	@mkdir -p build/bin
 	$(CXX) $(CXXFLAGS) -o $@ $(HOST_SRCS) -Lstencil_amd -lstencil_hip -Wl,-rpath,'$$ORIGIN/../../stencil_amd'
 
-oracle:
-	$(MAKE) -C oracle
+# one recipe builds liboracle.so (a second `$(MAKE) -C oracle` here raced it under -j: two compilers
+# writing the same file while $(FAKE) linked against it)
+oracle: oracle/liboracle.so
 	bash oracle/ref/build.sh
 
 oracle/liboracle.so: oracle/oracle.c oracle/oracle_impl.inc oracle/oracle.h

@@ -34,10 +34,20 @@ the north star's own 4096^3 fp64 7-point grid, 2 GPUs or more).  Slabs whose
 two grids do not fit a GPU keep ONE grid plus a rolling margin
 (STENCIL_SLAB_ROLLING), as C3 / C4 do on one GPU.
 
-Rank 0 prints one JSON line with the whole-job rate, the live roofline of the
-dominant kernel (compulsory bytes per launch / average launch time from HIP
-events on the kernel's own stream), and a bounded CPU baseline (the oracle's
-restatement of the reference's naive sweep, N=1 only).
+Rank 0 prints one JSON line with the whole-job rate and the live roofline of
+the dominant kernel (compulsory bytes per launch / average launch time from
+HIP events on the kernel's own stream).  A plain run sets up, warms up, times
+--steps sweeps and prints the line; --full adds the runs of their own beside
+the headline figure: a bounded CPU baseline (the oracle's restatement of the
+reference's naive sweep, one thread and all cores, N=1 only) and the
+copy-kernel bandwidth calibration (roofline.copy_kernel_GBps).
+
+--dump-outputs DIR writes what the last timed step left, as DIR/<name>.npy in
+the grid's dtype: plane_sums (every plane's sum, float64) and final_grid (a
+grid up to 32 MB) or final_grid_sample (whole x rows at fixed seeded (z, y) of
+a larger one, with final_grid_sample_z / _y, the indices).  The initial
+condition is fixed (--init), so two builds run with the same arguments can be
+compared file for file.
 """
 from __future__ import annotations
 
@@ -145,8 +155,16 @@ def parse(argv=None):
                     help="initial grid: the reference's (interior 0, x-ghost faces 1; the default) or a developed "
                          "field (uniform random [0,1) interior, splitmix64(seed 1 + cell index)): the box runs "
                          "12-18 %% faster on the reference's mostly-zero field (DVFS), DESIGN.md §6")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines (1 thread and all "
+                         "cores) and the copy-kernel bandwidth calibration of the roofline; without it the line's "
+                         "cpu_baseline is null and roofline.copy_kernel_GBps is absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step left to DIR/<name>.npy (the grid's "
+                         "dtype): the final grid, or a fixed seeded sample of a grid over 32 MB with the sample's "
+                         "indices, and every plane's sum")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baselines")
     ap.add_argument("--no-check", action="store_true",
                     help="N>1: skip the bitwise check against the global grid run as one grid on rank 0")
     ap.add_argument("--slab-timeout-ms", type=int, default=0,
@@ -413,6 +431,61 @@ def global_grid_check(spec, grid, sweeps, got, device, init="reference"):
         return {"error": f"{type(exc).__name__}: {exc}"[:300]}
 
 
+# ------------------------------------------------------------- --dump-outputs
+DUMP_BLOCK_BYTES = 32 << 20  # a grid up to this is written whole, a larger one as a sampled block of this size
+DUMP_SEED = 2024
+DUMP_PLANES = 8  # z planes of a sampled 3D block
+
+
+def sample_indices(n: int, count: int, rng):
+    """`count` of range(n), sorted: both ends, their neighbours and the middle
+    (where the reference initial condition's fronts are), then seeded picks."""
+    import numpy as np
+    if count >= n:
+        return np.arange(n, dtype=np.int64)
+    fixed = list(dict.fromkeys([0, n - 1, 1, n - 2, n // 2]))[:count]
+    rest = np.setdiff1d(np.arange(n, dtype=np.int64), fixed)
+    picks = rng.choice(rest, size=count - len(fixed), replace=False)
+    return np.sort(np.concatenate([np.asarray(fixed, dtype=np.int64), picks]))
+
+
+def dump_arrays(out_dir: str, arrays: dict):
+    """DIR/<name>.npy, float32 or float64 each."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        np.save(os.path.join(out_dir, name + ".npy"), arr if arr.dtype == np.float32 else arr.astype(np.float64))
+
+
+def dump_grid(out_dir: str, view, plane_sums):
+    """The final grid of a single-grid job: `view` is its interior on the
+    device, (nz, ny, nx) or (ny, nx).  Up to DUMP_BLOCK_BYTES it is written
+    whole (final_grid); a larger one as whole x rows at sampled (z, y)
+    (final_grid_sample, with the z and y indices beside it: the same ones for
+    the same shape, from DUMP_SEED), gathered on the device.  plane_sums
+    covers every cell either way."""
+    import numpy as np
+    import torch
+    arrays = {"plane_sums": plane_sums}
+    if view.numel() * view.element_size() <= DUMP_BLOCK_BYTES:
+        arrays["final_grid"] = view.cpu().numpy()
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        rows = DUMP_BLOCK_BYTES // (view.shape[-1] * view.element_size())
+        if view.dim() == 3:
+            zs = sample_indices(view.shape[0], DUMP_PLANES, rng)
+            ys = sample_indices(view.shape[1], max(1, rows // len(zs)), rng)
+            block = view[torch.from_numpy(zs).to(view.device)[:, None], torch.from_numpy(ys).to(view.device)[None, :]]
+            arrays["final_grid_sample_z"] = zs
+        else:
+            ys = sample_indices(view.shape[0], max(1, rows), rng)
+            block = view[torch.from_numpy(ys).to(view.device)]
+        arrays["final_grid_sample_y"] = ys
+        arrays["final_grid_sample"] = block.cpu().numpy()
+    dump_arrays(out_dir, arrays)
+
+
 # ------------------------------------------------------------------- drivers
 def main(argv=None):
     args = parse(argv)
@@ -460,6 +533,8 @@ def main_single(args):
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         kernel_ms_total = dev_ms
+        if args.dump_outputs:
+            dump_grid(args.dump_outputs, grid.interior(), grid.plane_sums())
         cells_per_launch = float(gnx) * gny * gnz  # charged per pass of K sweeps over the whole grid
         extra = dict(settle_config(0, 0.0, "none beyond the warm-up sweeps"),
                      rolling={"shift_planes": shift, "launch_planes": shift - sweeps_per_launch,
@@ -491,9 +566,11 @@ def main_single(args):
         eng.iterate(args.warmup)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        _, kernel_ms_total = eng.iterate(args.steps, stream=torch.cuda.current_stream(), timed=True)
+        fin, kernel_ms_total = eng.iterate(args.steps, stream=torch.cuda.current_stream(), timed=True)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_grid(args.dump_outputs, eng.interior(fin), eng.plane_sums(fin))
         kernel_launches = eng.plan(args.steps)[0]
         cells_per_launch = float(gnx) * gny * gnz
         extra, kernels_per_launch = settle_config(settle["launches"], settle["device_ms"],
@@ -513,7 +590,7 @@ def main_single(args):
                                else "tile-major packed z-chunk tables (a call of < %d sweeps)") % SUSTAINED_SWEEPS
         if long_job:
             key += "_long"
-        del eng
+        del eng, fin
     # device time per `sweeps_per_launch` sweeps, charged pro rata (with K = 4
     # a 1000-step job is 250 fused launches; a K that does not divide the step
     # count adds a remainder pair / single sweep)
@@ -543,9 +620,11 @@ def main_2d(args):
     eng.iterate(args.warmup)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    _, dev_ms = eng.iterate(args.steps, stream=torch.cuda.current_stream(), timed=True)
+    fin, dev_ms = eng.iterate(args.steps, stream=torch.cuda.current_stream(), timed=True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_grid(args.dump_outputs, eng.interior(fin), eng.plane_sums(fin))
     sweeps_per_launch = args.steps / max(1, launches)
     launch_ms = dev_ms / max(1, launches)
     report(args, pre, spec, "tb2ds", (nx, ny, 1), 1, elapsed, launch_ms, float(nx) * ny, sweeps_per_launch,
@@ -625,6 +704,9 @@ def rank_job_run(args, world, rank, device, spec, grid, rolling, uid, lib=None, 
             barrier()
         elapsed = job.run(args.steps) * 1e-3  # this rank's rounds, its device synchronised at both ends
         sweeps += args.steps
+        if getattr(args, "dump_outputs", None):  # this rank's planes, before the extra rounds advance them
+            dump_arrays(args.dump_outputs, {f"plane_sums_rank{rank}":
+                                            job.plane_sums()[info["first"]:info["first"] + info["planes"]]})
         extra = k * max(4, min(args.steps // max(1, k), 8))
         job.kernel_timing(True)
         job.run(extra)
@@ -778,6 +860,8 @@ def main_slab_job(args):
     job.run(args.warmup)
     elapsed = job.run(args.steps) * 1e-3  # host wall time, every device synchronised at both ends
     sweeps += args.steps
+    if args.dump_outputs:  # before the extra rounds below advance the grid
+        dump_arrays(args.dump_outputs, {"plane_sums": job.plane_sums()})
     extra = k * max(4, min(args.steps // max(1, k), 8))
     job.kernel_timing(True)
     job.run(extra)
@@ -942,13 +1026,14 @@ def report(args, pre, spec, kname, grid, n_gpus, elapsed, launch_ms, cells_per_l
         # above the compulsory bytes = re-reads (tile rings, halos)
         out["roofline"]["traffic_GBps"] = round(traffic / (launch_ms * 1e-3) / 1e9, 1)
         out["roofline"]["traffic_frac"] = round(out["roofline"]["traffic_GBps"] / HBM_PEAK_GBPS, 4)
-    if calibrate:
+    full = getattr(args, "full", False)  # runs of their own, beside the headline's: --full only
+    if calibrate and full:
         try:
             from stencil_amd.engine import copy_bandwidth
             out["roofline"]["copy_kernel_GBps"] = round(copy_bandwidth(1 << 30, reps=10, device=local), 1)
         except Exception as exc:  # calibration only
             out["roofline"]["copy_kernel_GBps"] = f"unavailable: {exc}"
-    if cpu and not args.no_cpu_baseline:
+    if cpu and full and not args.no_cpu_baseline:
         cb = dict(dtype=spec.dtype, shape=spec.shape)
         if cpu_full:  # the whole 2D config on the host (C1: 1024^2 x steps)
             n = gnx

@@ -131,3 +131,49 @@ def test_rank_of_parses_for_the_north_star():
     assert a.rank_of == 2 and a.gpus == 1
     plan = bench.slab_plan("NS4096", a.rank_of, BOX_FREE)
     assert plan["planes_per_slab"] == 2048 and plan["rolling"]
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.parse(["--full", "--dump-outputs", "some/dir"])
+    assert b.full is True and b.dump_outputs == "some/dir"
+
+
+@pytest.mark.parametrize("n,count", [(512, 8), (4096, 256), (6, 5), (5, 8), (1, 3)])
+def test_sample_indices_are_fixed_sorted_and_keep_the_ends(n, count):
+    import numpy as np
+    got = bench.sample_indices(n, count, np.random.default_rng(bench.DUMP_SEED))
+    again = bench.sample_indices(n, count, np.random.default_rng(bench.DUMP_SEED))
+    assert np.array_equal(got, again)
+    assert len(got) == min(n, count) == len(set(got.tolist()))
+    assert np.all(np.diff(got) > 0) and got[0] == 0 and got[-1] == n - 1
+    assert 0 <= got.min() and got.max() < n
+
+
+def test_dump_grid_whole_and_sampled(tmp_path, monkeypatch):
+    """A grid up to the block size is written whole in its own dtype; a larger
+    one as whole x rows at the sampled (z, y), with the indices beside it."""
+    import numpy as np
+    import torch
+    g = torch.arange(12 * 10 * 16, dtype=torch.float32).reshape(12, 10, 16)
+    sums = g.double().sum(dim=(1, 2)).numpy()
+    bench.dump_grid(str(tmp_path / "whole"), g, sums)
+    whole = np.load(tmp_path / "whole" / "final_grid.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, g.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "plane_sums.npy"), sums)
+    monkeypatch.setattr(bench, "DUMP_BLOCK_BYTES", 8 * 4 * 16 * 4)  # 8 planes x 4 rows of 16 fp32
+    bench.dump_grid(str(tmp_path / "part"), g, sums)
+    zs = np.load(tmp_path / "part" / "final_grid_sample_z.npy").astype(np.int64)
+    ys = np.load(tmp_path / "part" / "final_grid_sample_y.npy").astype(np.int64)
+    part = np.load(tmp_path / "part" / "final_grid_sample.npy")
+    assert len(zs) == 8 and len(ys) == 4 and part.dtype == np.float32
+    assert np.array_equal(part, g.numpy()[zs[:, None], ys[None, :]])
+    assert not os.path.exists(tmp_path / "part" / "final_grid.npy")
+    g2 = g[0].double()  # 2D: rows only
+    monkeypatch.setattr(bench, "DUMP_BLOCK_BYTES", 4 * 16 * 8)  # 4 rows of 16 fp64
+    bench.dump_grid(str(tmp_path / "part2d"), g2, g2.sum(dim=1).numpy())
+    ys = np.load(tmp_path / "part2d" / "final_grid_sample_y.npy").astype(np.int64)
+    assert len(ys) == 4 and {0, 9} <= set(ys.tolist())
+    part = np.load(tmp_path / "part2d" / "final_grid_sample.npy")
+    assert part.dtype == np.float64 and np.array_equal(part, g2.numpy()[ys])

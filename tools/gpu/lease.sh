@@ -6,8 +6,8 @@
 #   tests            the whole -m gpu suite
 #   tests:<files>    -m gpu on the comma-separated test files
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's command (bench.py --gpus 1 --steps 20 --warmup 5)
-#   bench:<cfg>      bench.py --config <cfg> (C1..C5, NS) at its usual length
+#   bench            the driver's command with the CPU baselines (bench.py --gpus 1 --steps 20 --warmup 5 --full)
+#   bench:<cfg>      bench.py --config <cfg> --full (C1..C5, NS) at its usual length
 #   bench1000        the default 1000-step C2 bench
 #   benchr:<cfg>     bench.py --config <cfg> --init random (a developed field)
 #   prof:<cfg>       profiles/collect.sh (kernel trace + FETCH/WRITE passes) of bench --config <cfg>
@@ -52,12 +52,12 @@ for step in "$@"; do
                > "$O/gpu_tests_k$n.txt" 2>&1 ;;
     smoke) timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 ;;
     bench) f="$O/bench_driver.json"; k2=1; while [ -e "$f" ]; do k2=$((k2 + 1)); f="$O/bench_driver_$k2.json"; done
-           timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$f" 2>> "$O/bench.err" ;;
+           timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$f" 2>> "$O/bench.err" ;;
     bench1000) f="$O/bench_1000.json"; k2=1; while [ -e "$f" ]; do k2=$((k2 + 1)); f="$O/bench_1000_$k2.json"; done
              timeout -k 10 200 python3 bench.py --steps 1000 --warmup 20 --no-cpu-baseline > "$f" 2>> "$O/bench.err" ;;
     bench:*) c=${step#bench:}
              case "$c" in C1) a="--steps 100 --warmup 10";; C5) a="--steps 32 --warmup 4";; *) a="--steps 40 --warmup 4";; esac
-             timeout -k 10 400 python3 bench.py --config "$c" $a > "$O/bench_$c.json" 2>> "$O/bench.err" ;;
+             timeout -k 10 400 python3 bench.py --config "$c" $a --full > "$O/bench_$c.json" 2>> "$O/bench.err" ;;
     benchr:*) c=${step#benchr:}   # the same on a developed field (uniform random interior)
              case "$c" in C1) a="--steps 100 --warmup 10";; C5) a="--steps 32 --warmup 4";; *) a="--steps 40 --warmup 4";; esac
              timeout -k 10 400 python3 bench.py --config "$c" --init random $a --no-cpu-baseline \
