@@ -360,6 +360,45 @@ int stencil_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches
 int stencil_plane_sums(const stencil_layout* l, const void* dev, double* plane_sums_host,
                        void* stream);
 
+/* Convergence-controlled runs.  The reference runs a fixed count
+ * (stencil.cpp:23-57); a Jacobi solver is normally driven until the update
+ * falls below a tolerance.
+ *
+ * stencil_diff_norms: for two grids of one layout and every slow-axis unit u
+ * in [begin, end) (a plane in 3D, a row in 2D),
+ *   max_abs[u - begin] = max |d|,  sum_sq[u - begin] = sum d*d,
+ *   d = double(a) - double(b), over the unit's interior cells only
+ * (kernels_norm.hip: one streaming read of both grids; the result depends on
+ * the layout and the data alone, never on the device, the stream or timing).
+ * If any d of a unit is NaN both outputs of that unit are NaN; infinities
+ * propagate.  max_abs / sum_sq: end - begin doubles each, HOST arrays, either
+ * may be NULL (not both).  Queued on `stream`, then synchronises it.  The
+ * scalar norm of the pair is, for STENCIL_NORM_MAX, the maximum of max_abs,
+ * and for STENCIL_NORM_L2 the square root of the sum of sum_sq taken in
+ * ascending unit order on the host; NaN if any unit is NaN.
+ *
+ * stencil_iterate_until: sweeps from grid `a` (as stencil_iterate) in blocks of
+ * min(check_every, max_iterations - done): block - 1 sweeps by
+ * stencil_iterate's own plan, then ONE single sweep, so that the two grids
+ * hold u^(n-1) and u^n (a K-step launch leaves u^n and u^(n-K)); then the
+ * scalar norm of u^n - u^(n-1).  Stops with *converged = 1 when norm <= tol,
+ * with *converged = 0 when the norm is NaN or max_iterations sweeps are done
+ * (a final block shorter than check_every is checked too).  Not converging is
+ * a result, not an error: STENCIL_OK either way.  max_iterations = 0:
+ * *iterations_done = 0, *converged = 0, *last_norm = +inf.  The grid
+ * *final_in_b names is bitwise stencil_iterate's after *iterations_done
+ * sweeps.  *elapsed_ms (optional): hipEvent time from the first launch to the
+ * completion of the last check.  Blocks the host once per check.
+ * STENCIL_EINVAL: check_every = 0, tol < 0 or NaN, an unknown norm, a == b or
+ * NULL grids; diff_norms: begin < 0, end > slow extent, begin > end. */
+enum { STENCIL_NORM_MAX = 0, STENCIL_NORM_L2 = 1 };
+int stencil_diff_norms(const stencil_layout* l, const void* a, const void* b, int64_t begin, int64_t end,
+                       double* max_abs, double* sum_sq, void* stream);
+int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t max_iterations,
+                          uint32_t check_every, int32_t norm, double tol, void* stream,
+                          uint32_t* iterations_done, int* final_in_b, double* last_norm,
+                          int* converged, float* elapsed_ms);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,

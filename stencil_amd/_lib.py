@@ -35,6 +35,8 @@ HALO_LO, HALO_HI = 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 SLAB_PERIODIC, SLAB_ROLLING = 1, 2
 SLAB_ID_BYTES = 128
+NORM_MAX, NORM_L2 = 0, 1
+NORM_NAMES = {"max": NORM_MAX, "l2": NORM_L2}
 
 KERNEL_NAMES = {"auto": KERNEL_AUTO, "direct": KERNEL_DIRECT, "zmarch": KERNEL_ZMARCH, "temporal2": KERNEL_TEMPORAL2,
                 "temporalk": KERNEL_TEMPORALK, "persistent": KERNEL_PERSISTENT}
@@ -57,7 +59,7 @@ EXPORTED_SYMBOLS = (
     "stencil_slab_create2", "stencil_slab_create_rank2", "stencil_slab_rolling_info", "stencil_slab_round_form",
     "stencil_slab_set_timeout", "stencil_prepare2", "stencil_slab_exchange_time",
     "stencil_sweepk_signal_gated", "stencil_exchange_done", "stencil_slab_round_info", "stencil_pack_table",
-    "stencil_slab_exchange_budget",
+    "stencil_slab_exchange_budget", "stencil_diff_norms", "stencil_iterate_until",
 )
 
 
@@ -163,6 +165,11 @@ def signatures() -> dict:
         "stencil_plan": (c_int, [L, c_uint32, POINTER(c_int64), POINTER(c_int32)]),
         "stencil_plane_sums": (c_int, [L, c_void_p, POINTER(c_double), c_void_p]),
         "stencil_copy_bandwidth": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, POINTER(c_float)]),
+        "stencil_diff_norms": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, POINTER(c_double), POINTER(c_double),
+                                       c_void_p]),
+        "stencil_iterate_until": (c_int, [L, c_void_p, c_void_p, c_uint32, c_uint32, c_int32, c_double, c_void_p,
+                                          POINTER(c_uint32), POINTER(c_int), POINTER(c_double), POINTER(c_int),
+                                          POINTER(c_float)]),
         "stencil_sweepk_geometry": (c_int, [L, c_int64, c_int64, c_int32, POINTER(c_int64), POINTER(c_int32),
                                             POINTER(c_int32)]),
         "stencil_sweepk_signal": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,

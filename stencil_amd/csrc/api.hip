@@ -6,10 +6,12 @@
 // dma_slave_pack, rma} that replace the Sunway CPE kernels
 // (src/stencil/slave/stencil_slave.hpp:26-46).
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -1050,6 +1052,147 @@ int stencil_plane_sums(const stencil_layout* l, const void* dev, double* plane_s
     if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
     (void)hipFree(d);
     if (e != hipSuccess) return set_error(STENCIL_EHIP, "plane sums failed: %s", hipGetErrorString(e));
+    return STENCIL_OK;
+}
+
+}  // extern "C"
+
+namespace stencil {
+namespace {
+
+// Device scratch of the norm kernels, stream-ordered (no device-wide wait).
+struct NormScratch {
+    double* dev = nullptr;
+    hipStream_t s = nullptr;
+    ~NormScratch() {
+        if (dev) (void)hipFreeAsync(dev, s);
+    }
+};
+
+// The per-unit norms of a - b over [begin, end) into host[0 .. n) (maxima) and
+// host[n .. 2n) (sums), n = end - begin; blocks until they have arrived.
+int norms_to_host(const stencil_layout& l, const void* a, const void* b, int64_t begin, int64_t end, double* scratch,
+                  double* host, hipStream_t s) {
+    if (int rc = launch_diff_norms(l, a, b, begin, end, scratch, s)) return rc;
+    if (end > begin)
+        STENCIL_HIP_CHECK(hipMemcpyAsync(host, scratch, size_t(2 * (end - begin)) * sizeof(double), hipMemcpyDeviceToHost, s));
+    STENCIL_HIP_CHECK(hipStreamSynchronize(s));
+    return STENCIL_OK;
+}
+
+// The scalar norm of a pair of grids from its per-unit values: the maximum of
+// the maxima, or the root of the sums added in ascending unit order; NaN when
+// any unit is NaN.
+double scalar_norm(const double* host, int64_t n, int32_t norm) {
+    double m = 0.0, s = 0.0;
+    bool nan = false;
+    for (int64_t u = 0; u < n; ++u) {
+        nan = nan || host[u] != host[u];
+        m = std::max(m, host[u]);
+        s += host[n + u];
+    }
+    if (nan) return std::numeric_limits<double>::quiet_NaN();
+    return norm == STENCIL_NORM_MAX ? m : std::sqrt(s);
+}
+
+}  // namespace
+}  // namespace stencil
+
+extern "C" {
+
+int stencil_diff_norms(const stencil_layout* l, const void* a, const void* b, int64_t begin, int64_t end,
+                       double* max_abs, double* sum_sq, void* stream) {
+    if (int rc = check_layout(l)) return rc;
+    if (!a || !b || a == b) return set_error(STENCIL_EINVAL, "need two distinct grids");
+    if (!max_abs && !sum_sq) return set_error(STENCIL_EINVAL, "need max_abs or sum_sq");
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "unit range [%lld, %lld) out of bounds [0, %lld)", (long long)begin,
+                         (long long)end, (long long)stencil_slow_extent(l));
+    const int64_t n = end - begin;
+    hipStream_t s = as_stream(stream);
+    if (n > 0) {
+        NormScratch sc;
+        sc.s = s;
+        STENCIL_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sc.dev), size_t(diff_norms_workspace_bytes(*l, n)), s));
+        std::vector<double> host(size_t(2 * n));
+        if (int rc = norms_to_host(*l, a, b, begin, end, sc.dev, host.data(), s)) return rc;
+        if (max_abs) std::copy_n(host.data(), n, max_abs);
+        if (sum_sq) std::copy_n(host.data() + n, n, sum_sq);
+    } else {
+        STENCIL_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t max_iterations, uint32_t check_every,
+                          int32_t norm, double tol, void* stream, uint32_t* iterations_done, int* final_in_b,
+                          double* last_norm, int* converged, float* elapsed_ms) {
+    if (int rc = check_layout(l)) return rc;
+    if (!a || !b || a == b) return set_error(STENCIL_EINVAL, "need two distinct grids");
+    if (check_every == 0) return set_error(STENCIL_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0.0)) return set_error(STENCIL_EINVAL, "tol must be a number >= 0");
+    if (norm != STENCIL_NORM_MAX && norm != STENCIL_NORM_L2) return set_error(STENCIL_EINVAL, "bad norm %d", norm);
+    hipStream_t s = as_stream(stream);
+    const int64_t n = stencil_slow_extent(l);
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    NormScratch sc;
+    sc.s = s;
+    std::vector<double> host(size_t(2 * n));
+    uint32_t done = 0;
+    int conv = 0;
+    double last = std::numeric_limits<double>::infinity();
+    void* cur = a;  // the grid that holds the newest sweep
+    void* old = b;
+    if (max_iterations > 0) {
+        if (elapsed_ms) {
+            STENCIL_HIP_CHECK(hipEventCreate(&ev.e0));
+            STENCIL_HIP_CHECK(hipEventCreate(&ev.e1));
+            STENCIL_HIP_CHECK(hipEventRecord(ev.e0, s));
+        }
+        if (n > 0)
+            STENCIL_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sc.dev), size_t(diff_norms_workspace_bytes(*l, n)), s));
+    }
+    while (done < max_iterations) {
+        const uint32_t block = std::min(check_every, max_iterations - done);
+        // block - 1 sweeps by stencil_iterate's own plan (its fused launches leave
+        // u^n and u^(n-K) in the two grids), then one single sweep, so that the
+        // grids hold u^(n-1) and u^n for the check
+        if (block > 1) {
+            int fin = 0;
+            if (int rc = stencil_iterate(l, cur, old, block - 1, stream, &fin, nullptr)) return rc;
+            if (fin) std::swap(cur, old);
+        }
+        if (int rc = launch_single(*l, cur, old, 0, n, s)) return rc;
+        std::swap(cur, old);
+        done += block;
+        if (int rc = norms_to_host(*l, cur, old, 0, n, sc.dev, host.data(), s)) return rc;
+        last = scalar_norm(host.data(), n, norm);
+        if (last <= tol) {
+            conv = 1;
+            break;
+        }
+        if (last != last) break;
+    }
+    if (elapsed_ms) {
+        *elapsed_ms = 0.f;
+        if (ev.e0) {
+            STENCIL_HIP_CHECK(hipEventRecord(ev.e1, s));
+            STENCIL_HIP_CHECK(hipEventSynchronize(ev.e1));
+            STENCIL_HIP_CHECK(hipEventElapsedTime(elapsed_ms, ev.e0, ev.e1));
+        }
+    }
+    if (iterations_done) *iterations_done = done;
+    if (final_in_b) *final_in_b = cur == b ? 1 : 0;
+    if (last_norm) *last_norm = last;
+    if (converged) *converged = conv;
+    clear_error();
     return STENCIL_OK;
 }
 

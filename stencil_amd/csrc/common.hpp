@@ -234,6 +234,14 @@ int tb2d_steps(const stencil_layout& l, uint32_t iterations);  // sweeps per lau
 bool tb2d1_fits(const stencil_layout& l);
 int launch_tb2d1(const stencil_layout& l, const void* in, void* out, uint32_t iterations, hipStream_t s);
 
+// kernels_norm.hip: per-unit max |a - b| and sum (a - b)^2 over the interior of
+// slow-axis units [begin, end), queued on `s`.  `scratch` (device memory,
+// diff_norms_workspace_bytes for end - begin units) then starts with the
+// end - begin maxima followed by the end - begin sums.
+int64_t diff_norms_workspace_bytes(const stencil_layout& l, int64_t units);
+int launch_diff_norms(const stencil_layout& l, const void* a, const void* b, int64_t begin, int64_t end, double* scratch,
+                      hipStream_t s);
+
 // Kernel-family coverage: the z-marching single-sweep family (7-point star
 // and 27-point box, r = 1) and the fused two-step family (same stencils).
 inline bool march_supported(const stencil_problem& p) { return zmarch_supports(p) || box27_supports(p); }

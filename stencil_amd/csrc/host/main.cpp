@@ -18,6 +18,15 @@ namespace {
 
 int g_status = 0;
 
+// With --tol: the one extra line of a run, and exit status 5 when it did not converge.
+void report_convergence(std::string_view method_name, ProgramOptions const& options, Stencil const& stencil) {
+    if (!options.until()) return;
+    std::cout << "[stencil-amd] " << method_name << (stencil.converged() ? ": converged after " : ": not converged after ")
+              << stencil.sweeps() << " sweeps, " << (options.norm_l2 ? "||delta||2" : "max|delta|") << " = "
+              << stencil.last_norm() << " (tol " << options.tol << ", every " << options.check_every << ")\n";
+    if (!stencil.converged() && g_status == 0) g_status = 5;
+}
+
 void run_test(std::string_view method_name, ProgramOptions const& options) {
     if (options.check_result) {
         std::cout << "Start to check the correctness of method " << method_name << ".\n";
@@ -28,6 +37,7 @@ void run_test(std::string_view method_name, ProgramOptions const& options) {
             g_status = 2;
             return;
         }
+        report_convergence(method_name, options, stencil);
 
         if (stencil.check_result()) {
             std::cout << "The results of method " << method_name << " is correct.\n";
@@ -41,6 +51,7 @@ void run_test(std::string_view method_name, ProgramOptions const& options) {
     std::chrono::steady_clock::duration total_duration = {};
     double total_device_ms = 0.0;
     double cells = 0.0;
+    double total_sweeps = 0.0;  // -i per run, or with --tol the sweeps each run did
 
     for (unsigned i = 0; i != options.repeat_count; ++i) {
         Stencil stencil(options);
@@ -64,6 +75,8 @@ void run_test(std::string_view method_name, ProgramOptions const& options) {
         std::cout << method_name << " Method spent "
                   << static_cast<std::chrono::duration<double, std::milli>>(*duration).count() << "ms for "
                   << options.iterations << " iterations.\n";
+        report_convergence(method_name, options, stencil);
+        total_sweeps += stencil.sweeps();
     }
 
     if (options.repeat_count == 0) return;  // the reference divides by zero here
@@ -73,7 +86,7 @@ void run_test(std::string_view method_name, ProgramOptions const& options) {
 
     const double dev_ms = total_device_ms / options.repeat_count;
     if (dev_ms > 0.0) {
-        const double gcell = cells * options.iterations / (dev_ms * 1e-3) / 1e9;
+        const double gcell = cells * (total_sweeps / options.repeat_count) / (dev_ms * 1e-3) / 1e9;
         const double bytes_per_update = 2.0 * (options.fp64 ? 8.0 : 4.0);
         std::cout << "[stencil-amd] " << method_name << (method_name == "CPU" ? ": host " : ": device ") << dev_ms
                   << " ms, " << gcell
@@ -103,7 +116,10 @@ int main(int argc, char** argv) {
                       << " exchange=" << (options->exchange_copy ? "copy" : "rccl") << " methods=";
             for (size_t i = 0; i < options->method_names.size(); ++i)
                 std::cout << (i ? "," : "") << options->method_names[i];
-            std::cout << "\n";
+            std::cout << " tol=";
+            if (options->until()) std::cout << options->tol;
+            else std::cout << "off";
+            std::cout << " check_every=" << options->check_every << " norm=" << (options->norm_l2 ? "l2" : "max") << "\n";
             return 0;
         }
         try {

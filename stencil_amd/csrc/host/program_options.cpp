@@ -5,6 +5,7 @@
 // not reproduced (CLI11 is not available to compare against).
 #include "program_options.hpp"
 
+#include <cctype>
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
@@ -14,7 +15,7 @@
 
 namespace {
 
-enum class Kind { Unsigned, Int64, Int, Str, Strs, Flag };
+enum class Kind { Unsigned, Int64, Int, Double, Str, Strs, Flag };
 
 struct Opt {
     char shortname;  // 0 = long-only
@@ -41,6 +42,16 @@ bool parse_i64(const std::string& s, int64_t& out) {
     errno = 0;
     char* end = nullptr;
     long long v = std::strtoll(s.c_str(), &end, 10);
+    if (errno || *end) return false;
+    out = v;
+    return true;
+}
+
+bool parse_double(const std::string& s, double& out) {
+    if (s.empty() || std::isspace(static_cast<unsigned char>(s[0]))) return false;
+    errno = 0;
+    char* end = nullptr;
+    const double v = std::strtod(s.c_str(), &end);
     if (errno || *end) return false;
     out = v;
     return true;
@@ -133,6 +144,12 @@ auto ProgramOptions::parse(int argc, char** argv) -> std::optional<ProgramOption
          [&](const std::string& v) { if (v != "rccl" && v != "copy") return false; r.exchange_copy = v == "copy"; return true; }},
         {0, "share-device", Kind::Flag, false, "[ext] Put every slab of a --gpus job on --device (rehearsal; --exchange copy).",
          [&](const std::string&) { r.share_device = true; return true; }},
+        {0, "tol", Kind::Double, false, "[ext] Sweep until one sweep's update is <= X (>= 0); -i becomes the cap.",
+         [&](const std::string& v) { double t; if (!parse_double(v, t) || !(t >= 0.0)) return false; r.tol = t; return true; }},
+        {0, "check-every", Kind::Unsigned, false, "[ext] Sweeps between two convergence checks of --tol. (default 100)",
+         [&](const std::string& v) { return parse_unsigned(v, r.check_every) && r.check_every >= 1; }},
+        {0, "norm", Kind::Str, false, "[ext] Norm of the update --tol compares: max (default) or l2.",
+         [&](const std::string& v) { if (v != "max" && v != "l2") return false; r.norm_l2 = v == "l2"; return true; }},
     };
 
     auto find_long = [&](const std::string& n) -> Opt* {

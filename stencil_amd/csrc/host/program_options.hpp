@@ -42,6 +42,11 @@ struct ProgramOptions {
     int gpus = 1;                  // --gpus N: 3D z-slab job over N GPUs (devices device .. device+N-1)
     bool exchange_copy = false;    // --exchange rccl|copy: halo transport of --gpus jobs
     bool share_device = false;     // --share-device: every slab on --device (needs --exchange copy)
+    double tol = -1.0;             // --tol X (>= 0): sweep until one sweep's update is <= X, -i is the cap; < 0 = off
+    unsigned check_every = 100;    // --check-every N (>= 1): sweeps between two checks
+    bool norm_l2 = false;          // --norm max|l2: the norm of the update
+
+    bool until() const { return tol >= 0.0; }
 
     int64_t extent_x() const { return nx >= 0 ? nx : matrix_size; }
     int64_t extent_y() const { return ny >= 0 ? ny : matrix_size; }

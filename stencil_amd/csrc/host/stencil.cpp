@@ -134,7 +134,12 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     if (method == CPU) return run_cpu(matrix, result);
     initialize_matrix();
     const bool ref_variant = method == DMA || method == DMA_STATIC_UNROLL || method == DMA_SLAVE_PACK || method == RMA;
-    if (method == HIP_MULTI_GPU || (options.gpus > 1 && !ref_variant)) return run_slabs(matrix, result);
+    if (method == HIP_MULTI_GPU || (options.gpus > 1 && !ref_variant)) {
+        if (options.until())
+            throw std::runtime_error("--tol covers single-GPU runs only: a slab job (HIPMultiGPU, --gpus > 1) has no "
+                                     "convergence check");
+        return run_slabs(matrix, result);
+    }
 
     stencil_problem p{};
     p.dims = options.dims;
@@ -203,6 +208,10 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
         // and the per-shape z-chunk schedule choice, timed on a shape's first
         // fused launch (kernels_strip.hip pick_schedule)
         check(stencil_prepare(&l, d.a, d.b, nullptr), "warm-up");
+        if (options.until()) {
+            std::vector<double> norms(size_t(stencil_slow_extent(&l)));
+            check(stencil_diff_norms(&l, d.a, d.b, 0, int64_t(norms.size()), norms.data(), nullptr, nullptr), "warm-up");
+        }
         upload(d.a, matrix);
         upload(d.b, result);
         check(stencil_synchronize(nullptr), "synchronize");
@@ -213,13 +222,25 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     int final_in_b = 0;
     float ms = 0.f;
     auto const start = std::chrono::steady_clock::now();
-    check(stencil_iterate(&l, d.a, d.b, options.iterations, nullptr, &final_in_b, &ms), "stencil_iterate");
+    if (options.until()) {
+        // -i is the cap: sweep until one sweep's update is <= --tol
+        uint32_t done = 0;
+        int conv = 0;
+        check(stencil_iterate_until(&l, d.a, d.b, options.iterations, options.check_every,
+                                    options.norm_l2 ? STENCIL_NORM_L2 : STENCIL_NORM_MAX, options.tol, nullptr, &done,
+                                    &final_in_b, &run_norm, &conv, &ms),
+              "stencil_iterate_until");
+        sweeps_done = done;
+        run_converged = conv != 0;
+    } else {
+        check(stencil_iterate(&l, d.a, d.b, options.iterations, nullptr, &final_in_b, &ms), "stencil_iterate");
+    }
     auto const end = std::chrono::steady_clock::now();
     device_ms = ms;
 
     // The final grid goes to the buffer the reference's parity rule names
     // (stencil.cpp:88-92,134): `result` after an odd count, else `matrix`.
-    BoundaryGrid<T>& dst = (options.iterations & 1u) ? result : matrix;
+    BoundaryGrid<T>& dst = (sweeps() & 1u) ? result : matrix;
     if (!synth) {
         check(stencil_download(&l, final_in_b ? d.b : d.a, dst.data(), dst.row_stride(), dst.rows_with_boundary(), nullptr),
               "download");
@@ -331,11 +352,51 @@ bool Stencil::naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iter
 // The method CPU: the reference's own CPU path (check_result's naive loop,
 // stencil.cpp:77-131) as a timed method on the host, single-threaded like the
 // reference; the final grid lands where the parity rule puts it.
+// The norm of one sweep's update, as stencil_iterate_until takes it: the
+// difference in double; max |d|, or the root of the sum of d*d added in
+// ascending z, y, x order.  NaN if any d is.
+template <class T>
+double Stencil::update_norm(const BoundaryGrid<T>& now, const BoundaryGrid<T>& before) const {
+    double m = 0.0, s = 0.0;
+    bool nan = false;
+    for (int64_t z = 0; z < now.depth(); ++z)
+        for (int64_t y = 0; y < now.height(); ++y)
+            for (int64_t x = 0; x < now.width(); ++x) {
+                const double d = double(now.elem_at(z, y, x)) - double(before.elem_at(z, y, x));
+                nan = nan || d != d;
+                m = std::max(m, std::fabs(d));
+                s += d * d;
+            }
+    if (nan) return std::nan("");
+    return options.norm_l2 ? std::sqrt(s) : m;
+}
+
 template <class T>
 auto Stencil::run_cpu(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) -> std::chrono::steady_clock::duration {
     initialize_matrix();
     auto const start = std::chrono::steady_clock::now();
-    naive_sweeps(matrix, result, options.iterations);
+    if (options.until()) {
+        // the stopping rule of stencil_iterate_until on the naive loop: blocks of
+        // --check-every sweeps (the last one shorter), the update checked after each
+        BoundaryGrid<T>* cur = &matrix;  // holds the newest sweep; the other grid the one before
+        BoundaryGrid<T>* old = &result;
+        sweeps_done = 0;
+        run_converged = false;
+        run_norm = HUGE_VAL;
+        while (sweeps_done < options.iterations) {
+            const unsigned block = std::min(options.check_every, options.iterations - sweeps_done);
+            if (naive_sweeps(*cur, *old, block)) std::swap(cur, old);
+            sweeps_done += block;
+            run_norm = update_norm(*cur, *old);
+            if (run_norm <= options.tol) {
+                run_converged = true;
+                break;
+            }
+            if (run_norm != run_norm) break;
+        }
+    } else {
+        naive_sweeps(matrix, result, options.iterations);
+    }
     auto const end = std::chrono::steady_clock::now();
     device_ms = std::chrono::duration<double, std::milli>(end - start).count();
     return end - start;
@@ -348,7 +409,7 @@ template <class T>
 bool Stencil::check_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const {
     BoundaryGrid<T> ga, gb;
     init_typed(ga, gb);
-    const bool swapped = naive_sweeps(ga, gb, options.iterations);
+    const bool swapped = naive_sweeps(ga, gb, sweeps());
     const BoundaryGrid<T>& in = swapped ? gb : ga;
     const BoundaryGrid<T>& compared = swapped ? result : matrix;
     for (int64_t z = 0; z < in.depth(); ++z)
@@ -374,7 +435,7 @@ auto Stencil::check_result() const -> bool {
 template <class T>
 bool Stencil::bmp_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result, const std::string& path) const {
     // The final grid is where the parity rule put it (stencil.cpp:134).
-    const BoundaryGrid<T>& g = (options.iterations & 1u) ? result : matrix;
+    const BoundaryGrid<T>& g = (sweeps() & 1u) ? result : matrix;
     if (g.empty()) return false;
     const int64_t z = g.depth() / 2;
     std::vector<BmpPixel> px;

@@ -54,12 +54,20 @@ public:
     double last_device_ms() const { return device_ms; }
     /// Interior cell count (one iteration updates each once).
     double cells() const;
+    /// Sweeps the last run did: -i, or with --tol the count at which it stopped.
+    unsigned sweeps() const { return options.until() ? sweeps_done : options.iterations; }
+    /// With --tol: did the last run's final check meet the tolerance, and its norm.
+    bool converged() const { return run_converged; }
+    double last_norm() const { return run_norm; }
 
 private:
     ProgramOptions options;
     BoundaryGrid<float> matrix32, result32;
     BoundaryGrid<double> matrix64, result64;
     double device_ms = 0.0;
+    unsigned sweeps_done = 0;
+    bool run_converged = false;
+    double run_norm = 0.0;
 
     template <class T>
     auto run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGrid<T>& result)
@@ -70,6 +78,8 @@ private:
     bool check_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const;
     template <class T>
     bool naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iterations) const;
+    template <class T>
+    double update_norm(const BoundaryGrid<T>& now, const BoundaryGrid<T>& before) const;
     template <class T>
     auto run_cpu(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) -> std::chrono::steady_clock::duration;
     template <class T>

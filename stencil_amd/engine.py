@@ -283,6 +283,63 @@ class JacobiEngine:
                                                _stream_handle(stream)), "stencil_plane_sums", lib=self.lib)
         return out
 
+    # ----------------------------------------------------------- convergence
+    def diff_norms(self, a: torch.Tensor, b: torch.Tensor, begin: int = 0, end: int | None = None, stream=None):
+        """Per-unit (max |a - b|, sum (a - b)^2) over the interior of slow-axis
+        units [begin, end), differences and squares in double
+        (stencil_diff_norms); two numpy float64 arrays of end - begin entries."""
+        end = self.slow_extent if end is None else end
+        n = max(0, end - begin)
+        max_abs, sum_sq = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(self.lib.stencil_diff_norms(ctypes.byref(self.layout), ctypes.c_void_p(a.data_ptr()),
+                                               ctypes.c_void_p(b.data_ptr()), begin, end, max_abs.ctypes.data_as(dp),
+                                               sum_sq.ctypes.data_as(dp), _stream_handle(stream)),
+                   "stencil_diff_norms", lib=self.lib)
+        return max_abs, sum_sq
+
+    def diff_norm(self, a: torch.Tensor, b: torch.Tensor, norm: str = "max", stream=None) -> float:
+        """The scalar norm of a - b over the interior: "max" = the largest
+        |difference|, "l2" = the root of the per-unit sums added in ascending
+        unit order; NaN if any unit is NaN."""
+        kind = _lib.NORM_NAMES[norm]
+        max_abs, sum_sq = self.diff_norms(a, b, stream=stream)
+        if np.isnan(max_abs).any():
+            return float("nan")
+        if kind == _lib.NORM_MAX:
+            return float(max_abs.max()) if max_abs.size else 0.0
+        total = 0.0
+        for v in sum_sq:
+            total += float(v)
+        return float(np.sqrt(total))
+
+    def iterate_until(self, tol: float, max_iterations: int, check_every: int = 100, norm: str = "max", stream=None,
+                      timed: bool = False) -> "UntilResult":
+        """Sweep from grid a until the norm of one sweep's update is <= tol,
+        checked every `check_every` sweeps and after the last one, at most
+        `max_iterations` sweeps (stencil_iterate_until).  The default of 100
+        is one check per job of the reference's own configuration."""
+        done, fin, conv = ctypes.c_uint32(0), ctypes.c_int(0), ctypes.c_int(0)
+        last, ms = ctypes.c_double(0.0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_iterate_until(ctypes.byref(self.layout), ctypes.c_void_p(self.a.data_ptr()),
+                                                  ctypes.c_void_p(self.b.data_ptr()), max_iterations, check_every,
+                                                  _lib.NORM_NAMES[norm], tol, _stream_handle(stream),
+                                                  ctypes.byref(done), ctypes.byref(fin), ctypes.byref(last),
+                                                  ctypes.byref(conv), ctypes.byref(ms) if timed else None),
+                   "stencil_iterate_until", lib=self.lib)
+        return UntilResult(self.b if fin.value else self.a, int(done.value), bool(conv.value), float(last.value),
+                           ms.value if timed else None)
+
+
+@dataclass(frozen=True)
+class UntilResult:
+    """What JacobiEngine.iterate_until returns."""
+    grid: torch.Tensor        # the grid that holds the last sweep
+    iterations: int           # sweeps done
+    converged: bool           # norm <= tol at the last check
+    norm: float               # the last check's norm (+inf when nothing ran)
+    ms: float | None          # device time, with timed=True
+
 
 class RollingGrid:
     """ONE resident grid plus `shift` spare planes (stencil_rolling_*): the
