@@ -277,8 +277,11 @@ int stencil_face_signal_read(const uint64_t* face_signal, uint64_t* value);  /* 
 int stencil_wait_face_signal(const uint64_t* face_signal, uint64_t target, void* stream);
 
 /* Whole job: `iterations` ping-pong sweeps starting from grid `a` (grid `b`
- * must hold the same ghosts). *final_in_b = 1 when the result is in `b`
- * (iterations odd), 0 when in `a` (parity rule, stencil.cpp:88-92,134).
+ * must hold the same ghosts). *final_in_b = 1 when the result is in `b`, 0
+ * when in `a`.  The grids swap once per LAUNCH: with one sweep per launch
+ * that is the parity rule (stencil.cpp:88-92,134: `b` when iterations is
+ * odd); a job of K-step launches ends wherever its launch count leaves it
+ * (23 sweeps of a 2D r = 1 job end in `a`), so read the flag.
  * With prob.kernel == TEMPORAL2, pairs of iterations run as one launch;
  * with TEMPORALK, K-tuples (remainder as a pair and/or a single sweep).
  * If elapsed_ms is non-NULL the call brackets its launches with hipEvents on
