@@ -85,7 +85,10 @@ int stencil_last_error(void);
  * workgroups run face-signalled rounds instead of staged ones),
  * STENCIL_SLAB_GATE=0 (face-signalled rounds wait for the exchange stream's
  * event before each launch instead of gating the launch's halo-reading
- * workgroups on the exchange-completion word: stencil_slab_round_info). */
+ * workgroups on the exchange-completion word: stencil_slab_round_info),
+ * STENCIL_UNTIL_FUSED=0 (stencil_iterate_until checks every block with a
+ * single sweep and stencil_diff_norms' kernels instead of the checking K-step
+ * launch, stencil_sweepk_update_max: the A/B lever and the fallback). */
 int stencil_debug_knobs(void);
 
 /* --------------------------------------------- 1. reference-compatible ABI */
@@ -230,6 +233,27 @@ int stencil_sweepk(const stencil_layout* l, const void* in, void* out, int64_t b
  * uploaded on first use).  Queries the current device. */
 int stencil_sweepk_geometry(const stencil_layout* l, int64_t begin, int64_t end, int32_t steps, int64_t* workgroups,
                             int32_t* zchunk, int32_t* packed);
+
+/* stencil_sweepk's K-step launch of the 3D r=1 naive 7-point star (steps
+ * 3..5; other steps STENCIL_EINVAL, other problems STENCIL_EUNSUPPORTED) that
+ * also reports the size of its LAST sweep's update: the launch raises
+ * *update_max_bits -- 8 bytes of DEVICE memory holding a double's bit pattern,
+ * zeroed by the caller -- to
+ *   max |double(u^K) - double(u^(K-1))|
+ * over exactly the cells it stores (the interior cells of planes [begin, end);
+ * never a ghost cell, a plane outside the range or a slab-halo plane the
+ * launch advances on the way).  The lane that stores a cell of u^K holds that
+ * cell's u^(K-1) in registers, so the value costs no memory traffic: each
+ * workgroup combines its lanes and issues at most one 64-bit atomic max on the
+ * bit pattern (non-negative doubles order as unsigned integers).  A maximum
+ * does not depend on the order it is taken in: the value is bit for bit the
+ * maximum of stencil_diff_norms' max_abs for the two grids.  If any such
+ * difference is NaN (inf - inf included) the word ends as a NaN pattern (they
+ * sort above +inf).  The word accumulates over launches; the launch is
+ * asynchronous on `stream`.  `out` is bitwise stencil_sweepk's.  NULL word:
+ * STENCIL_EINVAL. */
+int stencil_sweepk_update_max(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
+                              int32_t steps, uint64_t* update_max_bits, void* stream);
 
 /* Multi-GPU slabs: stencil_sweepk over [begin, end) (3D 7-point star, steps
  * 3..5; 27-point box, steps 2..4) as ONE launch whose workgroups add 1 to counters[0] as soon as the
@@ -381,10 +405,22 @@ int stencil_plane_sums(const stencil_layout* l, const void* dev, double* plane_s
  * ascending unit order on the host; NaN if any unit is NaN.
  *
  * stencil_iterate_until: sweeps from grid `a` (as stencil_iterate) in blocks of
- * min(check_every, max_iterations - done): block - 1 sweeps by
- * stencil_iterate's own plan, then ONE single sweep, so that the two grids
- * hold u^(n-1) and u^n (a K-step launch leaves u^n and u^(n-K)); then the
- * scalar norm of u^n - u^(n-1).  Stops with *converged = 1 when norm <= tol,
+ * min(check_every, max_iterations - done), each followed by the scalar norm of
+ * u^n - u^(n-1).  STENCIL_NORM_MAX on a job of K-step 7-point launches
+ * (stencil_plan: TEMPORALK), blocks of at least K sweeps: block - K sweeps by
+ * stencil_iterate's own plan, then ONE checking K-step launch
+ * (stencil_sweepk_update_max) whose 8-byte maximum is zeroed before it on the
+ * stream and copied back after it -- no extra sweep, no pass over the grids.
+ * Every other block (shorter ones, STENCIL_NORM_L2, the box, 2D, r > 1, forced
+ * kernel families; every block with STENCIL_UNTIL_FUSED=0): block - 1 sweeps
+ * by stencil_iterate's own plan, then ONE single sweep, so that the two grids
+ * hold u^(n-1) and u^n (a K-step launch leaves u^n and u^(n-K)), then
+ * stencil_diff_norms' kernels.  Both forms give the same sweep counts, norms
+ * (bit for bit) and final grid; which buffer holds it may differ, so read
+ * *final_in_b.  stencil_until_plan (host only, no device needed) reports the
+ * kernel launches of one block of `block` sweeps, its check included, and
+ * whether that check rides in the block's last launch.
+ * Stops with *converged = 1 when norm <= tol,
  * with *converged = 0 when the norm is NaN or max_iterations sweeps are done
  * (a final block shorter than check_every is checked too).  Not converging is
  * a result, not an error: STENCIL_OK either way.  max_iterations = 0:
@@ -393,7 +429,8 @@ int stencil_plane_sums(const stencil_layout* l, const void* dev, double* plane_s
  * sweeps.  *elapsed_ms (optional): hipEvent time from the first launch to the
  * completion of the last check.  Blocks the host once per check.
  * STENCIL_EINVAL: check_every = 0, tol < 0 or NaN, an unknown norm, a == b or
- * NULL grids; diff_norms: begin < 0, end > slow extent, begin > end. */
+ * NULL grids; diff_norms: begin < 0, end > slow extent, begin > end;
+ * until_plan: block = 0, an unknown norm. */
 enum { STENCIL_NORM_MAX = 0, STENCIL_NORM_L2 = 1 };
 int stencil_diff_norms(const stencil_layout* l, const void* a, const void* b, int64_t begin, int64_t end,
                        double* max_abs, double* sum_sq, void* stream);
@@ -401,6 +438,8 @@ int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t ma
                           uint32_t check_every, int32_t norm, double tol, void* stream,
                           uint32_t* iterations_done, int* final_in_b, double* last_norm,
                           int* converged, float* elapsed_ms);
+int stencil_until_plan(const stencil_layout* l, uint32_t block, int32_t norm, int64_t* launches,
+                       int32_t* fused_check);
 
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */

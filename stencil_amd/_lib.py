@@ -19,7 +19,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "libstencil_hip_debug.so")
 API_KNOBS = ("STENCIL_TK_STEPS", "STENCIL_BOX_STEPS", "STENCIL_TK_PACK", "STENCIL_BOXK_PACK", "STENCIL_SLAB_SIGNAL",
              "STENCIL_SLAB_CPWAIT", "STENCIL_SLAB_SERIAL", "STENCIL_SLAB_XCU", "STENCIL_SLAB_XCU_EXCL",
              "STENCIL_SLAB_TIMEOUT_MS", "STENCIL_SLAB_ROLLING_OVERLAP", "STENCIL_SLAB_STAGED", "STENCIL_SLAB_GATE",
-             "STENCIL_SLAB_PLACEMENTS", "STENCIL_SLAB_XCU_ALT")
+             "STENCIL_SLAB_PLACEMENTS", "STENCIL_SLAB_XCU_ALT", "STENCIL_UNTIL_FUSED")
 
 STENCIL_OK = 0
 ETIMEOUT = -6
@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "stencil_slab_set_timeout", "stencil_prepare2", "stencil_slab_exchange_time",
     "stencil_sweepk_signal_gated", "stencil_exchange_done", "stencil_slab_round_info", "stencil_pack_table",
     "stencil_slab_exchange_budget", "stencil_diff_norms", "stencil_iterate_until",
+    "stencil_sweepk_update_max", "stencil_until_plan",
 )
 
 
@@ -170,6 +171,8 @@ def signatures() -> dict:
         "stencil_iterate_until": (c_int, [L, c_void_p, c_void_p, c_uint32, c_uint32, c_int32, c_double, c_void_p,
                                           POINTER(c_uint32), POINTER(c_int), POINTER(c_double), POINTER(c_int),
                                           POINTER(c_float)]),
+        "stencil_sweepk_update_max": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+        "stencil_until_plan": (c_int, [L, c_uint32, c_int32, POINTER(c_int64), POINTER(c_int32)]),
         "stencil_sweepk_geometry": (c_int, [L, c_int64, c_int64, c_int32, POINTER(c_int64), POINTER(c_int32),
                                             POINTER(c_int32)]),
         "stencil_sweepk_signal": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,

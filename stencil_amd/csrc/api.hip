@@ -575,6 +575,22 @@ int stencil_sweepk(const stencil_layout* l, const void* in, void* out, int64_t b
     return rc;
 }
 
+int stencil_sweepk_update_max(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
+                              int32_t steps, uint64_t* update_max_bits, void* stream) {
+    if (int rc = check_layout(l)) return rc;
+    if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 3..5 (got %d)", steps);
+    if (!temporal2_supports(l->prob))
+        return set_error(STENCIL_EUNSUPPORTED, "update-max sweeps cover the 3D r=1 naive 7-point star only");
+    if (!update_max_bits) return set_error(STENCIL_EINVAL, "null update_max_bits");
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
+    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
+    const int rc = launch_tkstrip_update_max(*l, in, out, begin, end, steps,
+                                             reinterpret_cast<unsigned long long*>(update_max_bits), as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
 int stencil_sweepk_geometry(const stencil_layout* l, int64_t begin, int64_t end, int32_t steps, int64_t* workgroups,
                             int32_t* zchunk, int32_t* packed) {
     if (int rc = check_layout(l)) return rc;
@@ -1095,6 +1111,19 @@ double scalar_norm(const double* host, int64_t n, int32_t norm) {
     return norm == STENCIL_NORM_MAX ? m : std::sqrt(s);
 }
 
+// stencil_iterate_until: the sweeps of the checking K-step launch
+// (stencil_sweepk_update_max) that ends a block of `block` sweeps, or 0 when
+// the block keeps the un-fused check (single sweep + stencil_diff_norms): the
+// max norm on a job of K-step strip launches, blocks of at least K sweeps.
+// STENCIL_UNTIL_FUSED=0 (both libraries) keeps the un-fused check everywhere;
+// so does a forced strip shape or row layout (debug library).
+int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm) {
+    if (norm != STENCIL_NORM_MAX || api_knob("STENCIL_UNTIL_FUSED", 1) == 0) return 0;
+    if (knob("STENCIL_TK_STRIP", 1) != 1) return 0;
+    const int k = iterate_tk_steps(p);
+    return k > 0 && block >= uint32_t(k) ? k : 0;
+}
+
 }  // namespace
 }  // namespace stencil
 
@@ -1142,8 +1171,8 @@ int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t ma
             if (e1) (void)hipEventDestroy(e1);
         }
     } ev;
-    NormScratch sc;
-    sc.s = s;
+    NormScratch sc, word;  // word: the checking launches' 8-byte maximum
+    sc.s = word.s = s;
     std::vector<double> host(size_t(2 * n));
     uint32_t done = 0;
     int conv = 0;
@@ -1161,6 +1190,35 @@ int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t ma
     }
     while (done < max_iterations) {
         const uint32_t block = std::min(check_every, max_iterations - done);
+        if (const uint32_t k = uint32_t(until_fused_steps(l->prob, block, norm))) {
+            // block - K sweeps by stencil_iterate's own plan, then one K-step
+            // launch that also reports max |u^n - u^(n-1)| over the cells it
+            // stores (every interior cell): no single sweep, no norm pass
+            if (block > k) {
+                int fin = 0;
+                if (int rc = stencil_iterate(l, cur, old, block - k, stream, &fin, nullptr)) return rc;
+                if (fin) std::swap(cur, old);
+            }
+            if (!word.dev) STENCIL_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&word.dev), sizeof(uint64_t), s));
+            STENCIL_HIP_CHECK(hipMemsetAsync(word.dev, 0, sizeof(uint64_t), s));
+            if (int rc = launch_tkstrip_update_max(*l, cur, old, 0, n, int(k),
+                                                   reinterpret_cast<unsigned long long*>(word.dev), s))
+                return rc;
+            std::swap(cur, old);
+            done += block;
+            uint64_t bits = 0;
+            STENCIL_HIP_CHECK(hipMemcpyAsync(&bits, word.dev, sizeof bits, hipMemcpyDeviceToHost, s));
+            STENCIL_HIP_CHECK(hipStreamSynchronize(s));
+            // NaN patterns sort above +inf's: a NaN update reports the norm kernels' NaN
+            std::memcpy(&last, &bits, sizeof last);
+            if (last != last) last = std::numeric_limits<double>::quiet_NaN();
+            if (last <= tol) {
+                conv = 1;
+                break;
+            }
+            if (last != last) break;
+            continue;
+        }
         // block - 1 sweeps by stencil_iterate's own plan (its fused launches leave
         // u^n and u^(n-K) in the two grids), then one single sweep, so that the
         // grids hold u^(n-1) and u^n for the check
@@ -1192,6 +1250,21 @@ int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t ma
     if (final_in_b) *final_in_b = cur == b ? 1 : 0;
     if (last_norm) *last_norm = last;
     if (converged) *converged = conv;
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_until_plan(const stencil_layout* l, uint32_t block, int32_t norm, int64_t* launches, int32_t* fused_check) {
+    if (int rc = check_layout(l)) return rc;
+    if (block == 0) return set_error(STENCIL_EINVAL, "block must be at least 1");
+    if (norm != STENCIL_NORM_MAX && norm != STENCIL_NORM_L2) return set_error(STENCIL_EINVAL, "bad norm %d", norm);
+    const uint32_t k = uint32_t(until_fused_steps(l->prob, block, norm));
+    int64_t n = 0;
+    if (int rc = stencil_plan(l, k ? block - k : block - 1, &n, nullptr)) return rc;
+    // fused: the checking launch; else the single sweep and the norm's launches
+    n += k ? 1 : 1 + diff_norms_launches(*l, stencil_slow_extent(l));
+    if (launches) *launches = n;
+    if (fused_check) *fused_check = k ? 1 : 0;
     clear_error();
     return STENCIL_OK;
 }

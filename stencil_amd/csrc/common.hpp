@@ -205,6 +205,11 @@ struct StripGate {
 int launch_tkstrip_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                           unsigned* sig, unsigned long long* fsig, int* nsig, hipStream_t s,
                           const StripGate& gate = StripGate{});
+// The default strip shapes as plain launches that also raise *word (8 bytes of
+// device memory, a double's bit pattern) to max |u^K - u^(K-1)| over the cells
+// they store (stencil_sweepk_update_max)
+int launch_tkstrip_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
+                              unsigned long long* word, hipStream_t s);
 int launch_boxk(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                 hipStream_t s);
 int launch_boxk_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
@@ -239,6 +244,7 @@ int launch_tb2d1(const stencil_layout& l, const void* in, void* out, uint32_t it
 // diff_norms_workspace_bytes for end - begin units) then starts with the
 // end - begin maxima followed by the end - begin sums.
 int64_t diff_norms_workspace_bytes(const stencil_layout& l, int64_t units);
+int64_t diff_norms_launches(const stencil_layout& l, int64_t units);  // kernel launches of launch_diff_norms
 int launch_diff_norms(const stencil_layout& l, const void* a, const void* b, int64_t begin, int64_t end, double* scratch,
                       hipStream_t s);
 

@@ -171,6 +171,15 @@ int64_t diff_norms_workspace_bytes(const stencil_layout& l, int64_t units) {
     return (2 * units + 2 * batch * p.chunks) * int64_t(sizeof(double));
 }
 
+// Kernel launches launch_diff_norms makes for `units` units: a norm and a
+// combine launch per batch (host only).
+int64_t diff_norms_launches(const stencil_layout& l, int64_t units) {
+    if (units <= 0) return 0;
+    const NormPlan p = norm_plan(l);
+    const int64_t batch = std::min(units, std::max<int64_t>(1, kNormMaxBlocks / p.chunks));
+    return 2 * ((units + batch - 1) / batch);
+}
+
 int launch_diff_norms(const stencil_layout& l, const void* a, const void* b, int64_t begin, int64_t end, double* scratch,
                       hipStream_t s) {
     const int64_t units = end - begin;

@@ -262,8 +262,19 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // LDS serves as per-wave register space: 28 VGPRs per lane fewer at RY = 7,
 // for 7 ds_write_b64 + 28 ds_read_b64 per wave and step, which pays for one
 // more fused sweep (K = 5) at the same 7-row strips.
+// UMAX (stencil_sweepk_update_max): the launch also reports
+// max |t_K - t_{K-1}| over exactly the cells it stores -- the lane that stores
+// t_K(p-K) holds that cell's t_{K-1}(p-K) as stage K's centre operand, so the
+// last sweep's update costs no memory traffic.  Every lane keeps a running
+// maximum (the difference taken in double, as kernels_norm.hip does) and a
+// NaN flag over all of the workgroup's segments; at the end of the kernel the
+// waves combine by lane shuffles, then through LDS (the boundary-row buffers,
+// free by then), and one lane raises the device word `fsig` with at most one
+// 64-bit atomic max of the bit pattern: non-negative doubles order as
+// unsigned integers and NaN patterns sort above +inf, so the word is the same
+// whatever order the workgroups arrive in, and a NaN stays.
 template <typename T, int V, int RY, int NW, int K, bool DB, int DIAG = 0, bool SIG = false, int NS = 4, bool FP = true,
-          bool HL = false, bool TIER = false, bool SPLIT = false>
+          bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false>
 __global__ void __launch_bounds__(64 * NW)
     tkstrip_7pt(const T* __restrict__ in, T* __restrict__ out, Geom g, int zbeg, int zend, int zchunk,
                 int tiles_x, int tiles_y, int halo_lo, int halo_hi, T avg, unsigned* __restrict__ sig,
@@ -274,6 +285,8 @@ __global__ void __launch_bounds__(64 * NW)
     constexpr int XR = Tl::XR, TX = Tl::TX, TY = Tl::TY, RH = Tl::RH, RW = Tl::RW, NB = Tl::NB;
     constexpr int LW = Tl::LW, NSTR = Tl::NSTR;
     static_assert(!SPLIT || !TIER, "SPLIT: plain or face-signalled launches");
+    static_assert(!UMAX || (!TIER && !SIG && DIAG == 0 && !TK_SST && !TK_XRING8 && !TK_PROBE_NOBAR),
+                  "UMAX: plain launches of the product shapes only");
     constexpr bool SST = Tl::SSTS && !SIG && !TIER && !HL;
     constexpr int NI = (RY + 1) / 2;  // SST: row pairs per strip
     typedef T V4T __attribute__((ext_vector_type(4)));
@@ -386,6 +399,9 @@ __global__ void __launch_bounds__(64 * NW)
         // strongest at s = 1 (the widest reach): [za - K + 1, zb + K - 1)
         return za - (K - 1) >= (halo_lo ? -(K - 1) : 0) && zb + K - 1 <= (halo_hi ? nz + K - 1 : nz);
     };
+    // UMAX: this lane's max |t_K - t_{K-1}| over the cells it has stored, and whether one was NaN
+    double umax = 0.0;
+    bool unan = false;
     auto segment = [&](auto REV_, auto PROD_, auto SFAST_) {  // one segment: tile t, planes [za, zb)
     constexpr bool REV = decltype(REV_)::value;
     constexpr bool SFAST = decltype(SFAST_)::value;  // the whole segment without ghost-cell selects
@@ -599,6 +615,7 @@ __global__ void __launch_bounds__(64 * NW)
 #pragma unroll
         for (int k = 0; k < RY; ++k) {
             VT prev{};  // this row's result of the previous stage
+            VT ck{};    // UMAX: stage K's centre operand, t_{K-1}(p-K)
             auto stage = [&](auto s_) {
                 constexpr int s = decltype(s_)::value;
                 // t_{s-1} planes p-s (centre), p-s-1 (z-), p-s+1 (z+)
@@ -616,6 +633,7 @@ __global__ void __launch_bounds__(64 * NW)
                     up = k == 0 ? STRIP_ABOVE(s - 1) : hget(s - 1, (S - s + 4) & 1, k == 0 ? 0 : k - 1);
                     dn = k == RY - 1 ? STRIP_BELOW(s - 1) : hget(s - 1, (S - s + 4) & 1, k == RY - 1 ? 0 : k + 1);
                 }
+                if constexpr (UMAX && s == K) ck = c;
                 const T wl = sdpp<kSShr1>(c[V - 1]);
                 const T er = sdpp<kSShl1>(c[0]);
                 VT o;
@@ -685,6 +703,16 @@ __global__ void __launch_bounds__(64 * NW)
 #pragma unroll
                     for (int j = 0; j < V; ++j)
                         if (xst[j]) q[j] = prev[j];
+                }
+                if constexpr (UMAX) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) {
+                        if (xst[j]) {  // exactly the cells stored
+                            const double d = double(prev[j]) - double(ck[j]);
+                            unan = unan || d != d;
+                            umax = __builtin_fmax(umax, __builtin_fabs(d));  // drops a NaN: the flag keeps it
+                        }
+                    }
                 }
             }
         }
@@ -826,12 +854,30 @@ __global__ void __launch_bounds__(64 * NW)
             segment(F{}, F{}, F{});
         }
     }
+    if constexpr (UMAX) {
+        unsigned long long m = unan ? 0x7ff8000000000000ull : __builtin_bit_cast(unsigned long long, umax);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long v = __shfl_xor(m, o);
+            m = v > m ? v : m;
+        }
+        __syncthreads();  // every wave has read its last boundary rows: L is free
+        unsigned long long* red = reinterpret_cast<unsigned long long*>(&L[0][0][0][0][0]);
+        if (threadIdx.x == 0) red[threadIdx.y] = m;
+        __syncthreads();
+        if (threadIdx.x == 0 && threadIdx.y == 0) {
+            for (int i = 1; i < NW; ++i) m = red[i] > m ? red[i] : m;
+            // a word already at least as large needs no atomic (a stale load only costs one)
+            if (m > __hip_atomic_load(fsig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                __hip_atomic_fetch_max(fsig, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 int senv_int(const char* name, int dflt) { return knob(name, dflt); }
 
 template <typename T, int V, int RY, int NW, int K, bool DB = true, int DIAG = 0, bool SIG = false, int NS = 4,
-          bool FP = true, bool HL = false, bool SPLIT = false>
+          bool FP = true, bool HL = false, bool SPLIT = false, bool UMAX = false>
 int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, hipStream_t s,
               unsigned* sig = nullptr, int* nsig = nullptr, unsigned long long* fsig = nullptr,
               const StripGate& gate = StripGate{}) {
@@ -843,7 +889,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     if ((g.plane + g.row + 64) * int64_t(sizeof(T)) >= (int64_t(1) << 32) || g.nz + 2 * K >= (int64_t(1) << 30))
         return set_error(STENCIL_EINVAL, "plane too large for tkstrip (4 GiB per plane, 2^30 planes)");
     const int64_t gx = (g.nx + Tl::TX - 1) / Tl::TX, gy = (g.ny + Tl::TY - 1) / Tl::TY;
-    auto kern = tkstrip_7pt<T, V, RY, NW, K, DB, DIAG, SIG, NS, FP, HL, false, SPLIT>;
+    auto kern = tkstrip_7pt<T, V, RY, NW, K, DB, DIAG, SIG, NS, FP, HL, false, SPLIT, UMAX>;
     const int64_t tiles = gx * gy;
     int dev = 0, slots = 0;
     STENCIL_HIP_CHECK(hipGetDevice(&dev));
@@ -1604,6 +1650,36 @@ int launch_tkstrip_signal(const stencil_layout& l, const void* in, void* out, in
         }
     }
     return set_error(STENCIL_EINVAL, "face-signalled sweeps: steps must be 3, 4 or 5 (got %d)", steps);
+}
+
+// The default shapes reporting max |u^K - u^(K-1)| over the cells they store
+// (stencil_sweepk_update_max; UMAX above): plain launches through launch_st,
+// `word` travels in the kernel's fsig argument.  launch_tkstrip_signal's six
+// shapes, but for fp32 K = 4 (below).  DESIGN.md §5.6 has the resource table.
+int launch_tkstrip_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
+                              unsigned long long* word, hipStream_t s) {
+    if (!temporal2_supports(l.prob))
+        return set_error(STENCIL_EUNSUPPORTED, "update-max sweeps cover the 3D r=1 naive 7-point star only");
+    if (!word) return set_error(STENCIL_EINVAL, "null update_max_bits");
+    constexpr bool U = true;
+    if (l.prob.dtype == STENCIL_F32) {
+        switch (steps) {
+        case 3: return launch_st<float, 4, 4, 8, 3, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
+        // 6-row strips: the default 7-row shape (253 VGPRs) spills a VGPR once it holds the accumulator
+        // (8 B of scratch per lane); 6 rows take 223 and none.  Bitwise the same sweep (120 x 40 tiles).
+        case 4: return launch_st<float, 2, 6, 8, 4, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
+        case 5: return launch_st<float, 2, 5, 8, 5, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
+        default: break;
+        }
+    } else {
+        switch (steps) {
+        case 3: return launch_st<double, 2, 4, 8, 3, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
+        case 4: return launch_st<double, 1, 7, 8, 4, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
+        case 5: return launch_st<double, 1, 5, 8, 5, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
+        default: break;
+        }
+    }
+    return set_error(STENCIL_EINVAL, "update-max sweeps: steps must be 3, 4 or 5 (got %d)", steps);
 }
 
 #endif  // STRIP_ILP_TU

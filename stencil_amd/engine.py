@@ -173,6 +173,33 @@ class JacobiEngine:
                                            ctypes.c_void_p(dst.data_ptr()), begin, end, steps,
                                            _stream_handle(stream)), "stencil_sweepk", lib=self.lib)
 
+    def sweepk_update_max(self, src: torch.Tensor, dst: torch.Tensor, begin: int, end: int, steps: int,
+                          stream=None) -> float:
+        """sweepk over [begin, end) (3D 7-point star, steps 3..5) as the launch
+        that also reports its last sweep's update: returns
+        max |double(u^steps) - double(u^(steps-1))| over the cells it stored
+        (stencil_sweepk_update_max; NaN if any difference is).  Allocates and
+        zeroes the 8-byte device word, launches, waits for the stream."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            word = torch.zeros(1, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.stencil_sweepk_update_max(ctypes.byref(self.layout), ctypes.c_void_p(src.data_ptr()),
+                                                      ctypes.c_void_p(dst.data_ptr()), begin, end, steps,
+                                                      ctypes.c_void_p(word.data_ptr()), _stream_handle(s)),
+                   "stencil_sweepk_update_max", lib=self.lib)
+        s.synchronize()
+        return float(np.array([int(word.item())], dtype=np.int64).view(np.float64)[0])
+
+    def until_plan(self, block: int, norm: str = "max") -> dict:
+        """One block of `block` sweeps of iterate_until (stencil_until_plan, host
+        only): its kernel launches, the check's included, and whether the check
+        rides in the block's last launch."""
+        launches, fused = ctypes.c_int64(0), ctypes.c_int32(0)
+        _lib.check(self.lib.stencil_until_plan(ctypes.byref(self.layout), block, _lib.NORM_NAMES[norm],
+                                               ctypes.byref(launches), ctypes.byref(fused)),
+                   "stencil_until_plan", lib=self.lib)
+        return {"launches": int(launches.value), "fused_check": bool(fused.value)}
+
     def sweepk_geometry(self, steps: int, begin: int = 0, end: int | None = None) -> dict:
         """How sweepk(steps) over [begin, end) would launch the K-step strip
         kernel: workgroups, planes per z-chunk, packed schedule or not."""

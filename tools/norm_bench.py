@@ -13,12 +13,23 @@ Prints one JSON line:
                 the rate of the rest);
   (b) checks -- iterate_until(tol=0, 1000 sweeps, a check every 100) against
                 stencil_iterate(1000), device time of each, overhead in percent.
+
+    python tools/norm_bench.py --fused-ab [--rounds 3] [--parent-lib PATH] [--out FILE]
+
+The check that rides in the K-step launch against the un-fused one (DESIGN.md
+§5.6): the same checked jobs (a check every 100, 20 and 4 sweeps) with
+STENCIL_UNTIL_FUSED=0 and =1 -- and, with --parent-lib, with another build of
+libstencil_hip.so, e.g. the parent commit's -- each in a fresh child process,
+the arms alternating, `--rounds` children per arm.  Every child also times the
+checking launch against the plain launch of the same shape, interleaved.
+--nx/--ny/--nz give a grid that is not a cube; --launch-only skips the jobs.
 """
 import argparse
 import ctypes
 import json
 import os
 import statistics
+import subprocess
 import sys
 
 import torch
@@ -28,15 +39,145 @@ from stencil_amd import _lib
 from stencil_amd.engine import JacobiEngine, StencilSpec, _stream_handle
 
 
+EVERY = (100, 20, 4)
+
+
+def child(a):
+    """One arm in this (fresh) process: the fixed-count job, the checked jobs,
+    and the checking launch beside the plain one.  Prints one JSON line."""
+    if a.lib:  # another build of the library: bind what it exports
+        _lib.LIB_PATH = a.lib
+        probe, sigs = ctypes.CDLL(a.lib), _lib.signatures()
+        _lib.signatures = lambda: {k: v for k, v in sigs.items() if hasattr(probe, k)}
+    torch.cuda.set_device(0)
+    nx, ny, nz = a.nx or a.size, a.ny or a.size, a.nz or a.size
+    e = JacobiEngine(StencilSpec(dims=3, dtype=a.dtype), nx, ny, nz, device=0)
+    has = hasattr(e.lib, "stencil_sweepk_update_max")
+    out = {"fused_check": {str(ev): e.until_plan(ev) for ev in EVERY} if has else None, "steps": e.fuse_steps}
+
+    def fixed():
+        e.reset("reference")
+        e.prepare()
+        return e.iterate(a.sweeps, timed=True)[1]
+
+    def checked(every):
+        e.reset("reference")
+        e.prepare()
+        r = e.iterate_until(0.0, a.sweeps, check_every=every, timed=True)
+        assert r.iterations == a.sweeps and not r.converged
+        return r.ms
+
+    if not a.launch_only:
+        fixed(), [checked(ev) for ev in EVERY]  # first use: the shape's schedule trials
+        fixed_ms, checked_ms = [], {ev: [] for ev in EVERY}
+        for _ in range(a.reps):
+            fixed_ms.append(fixed())
+            for ev in EVERY:
+                checked_ms[ev].append(checked(ev))
+        out["iterate_ms"] = [round(t, 3) for t in fixed_ms]
+        out["iterate_until_ms"] = {str(ev): [round(t, 3) for t in v] for ev, v in checked_ms.items()}
+    if has:
+        k, n = e.fuse_steps, e.slow_extent
+        stream = torch.cuda.current_stream()
+        word = torch.zeros(1, dtype=torch.int64, device=e.device)
+
+        def launches(check, count=20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(count):
+                if check:
+                    _lib.check(e.lib.stencil_sweepk_update_max(ctypes.byref(e.layout), ctypes.c_void_p(e.a.data_ptr()),
+                                                               ctypes.c_void_p(e.b.data_ptr()), 0, n, k,
+                                                               ctypes.c_void_p(word.data_ptr()), _stream_handle(stream)),
+                               "stencil_sweepk_update_max", lib=e.lib)
+                else:
+                    e.sweepk(e.a, e.b, 0, n, k, stream=stream)
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / count
+
+        e.reset("random", 7)
+        launches(False, 2), launches(True, 2)  # the schedule trials
+        e.prepare()
+        plain, check = [], []
+        for _ in range(5):
+            plain.append(launches(False))
+            check.append(launches(True))
+        out["launch_ms"] = {"plain": [round(t, 4) for t in plain], "checking": [round(t, 4) for t in check]}
+    print(json.dumps(out))
+
+
+def spread(v):
+    return round(100.0 * (max(v) - min(v)) / statistics.median(v), 2)
+
+
+def fused_ab(a):
+    arms = [("unfused", {"STENCIL_UNTIL_FUSED": "0"}, None), ("fused", {"STENCIL_UNTIL_FUSED": "1"}, None)]
+    if a.parent_lib:
+        arms.append(("parent", {}, a.parent_lib))
+    runs = {name: [] for name, _, _ in arms}
+    base = [sys.executable, os.path.abspath(__file__), "--child", "--size", str(a.size), "--dtype", a.dtype,
+            "--reps", str(a.reps), "--sweeps", str(a.sweeps), "--nx", str(a.nx), "--ny", str(a.ny), "--nz", str(a.nz)]
+    if a.launch_only:
+        base.append("--launch-only")
+    for _ in range(a.rounds):  # alternating: every arm sees the same box at about the same time
+        for name, env, lib in arms:
+            full = {k: v for k, v in os.environ.items() if k != "STENCIL_UNTIL_FUSED"}
+            full.update(env)
+            p = subprocess.run(base + (["--lib", lib] if lib else []), capture_output=True, text=True, env=full)
+            if p.returncode != 0:
+                raise SystemExit(f"{name}: child failed\n{p.stdout}{p.stderr}")
+            runs[name].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    line = {"tool": "norm_bench --fused-ab", "grid": [a.nx or a.size, a.ny or a.size, a.nz or a.size], "dtype": a.dtype,
+            "sweeps": a.sweeps, "rounds": a.rounds, "arms": {}}
+    for name, rs in runs.items():
+        arm = {"fused_check": rs[0]["fused_check"], "steps": rs[0]["steps"]}
+        if not a.launch_only:
+            f = [t for r in rs for t in r["iterate_ms"]]
+            arm["iterate_ms"] = {"median": statistics.median(f), "spread_percent": spread(f), "all": f}
+            arm["iterate_until_ms"] = {}
+            for ev in EVERY:
+                c = [t for r in rs for t in r["iterate_until_ms"][str(ev)]]
+                arm["iterate_until_ms"][str(ev)] = {
+                    "median": statistics.median(c), "spread_percent": spread(c), "all": c,
+                    "overhead_percent": round(100.0 * (statistics.median(c) / statistics.median(f) - 1.0), 2)}
+        if "launch_ms" in rs[0]:
+            pl = [t for r in rs for t in r["launch_ms"]["plain"]]
+            ck = [t for r in rs for t in r["launch_ms"]["checking"]]
+            arm["launch_ms"] = {"plain_median": statistics.median(pl), "plain_spread_percent": spread(pl),
+                                "checking_median": statistics.median(ck), "checking_spread_percent": spread(ck),
+                                "checking_vs_plain_percent":
+                                    round(100.0 * (statistics.median(ck) / statistics.median(pl) - 1.0), 2)}
+        line["arms"][name] = arm
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--nx", type=int, default=0)
+    ap.add_argument("--ny", type=int, default=0)
+    ap.add_argument("--nz", type=int, default=0)
+    ap.add_argument("--fused-ab", action="store_true", help="the fused check against the un-fused one, in child processes")
+    ap.add_argument("--rounds", type=int, default=3, help="--fused-ab: children per arm")
+    ap.add_argument("--parent-lib", default=None, help="--fused-ab: a third arm, another build of libstencil_hip.so")
+    ap.add_argument("--launch-only", action="store_true", help="--fused-ab: only the launch timing")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dtype", default="fp64", choices=["fp32", "fp64"])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sweeps", type=int, default=1000)
     ap.add_argument("--check-every", type=int, default=100)
     ap.add_argument("--out", default=None, help="also write the line to this file")
     a = ap.parse_args()
+    if a.child:
+        return child(a)
+    if a.fused_ab:
+        return fused_ab(a)
     torch.cuda.set_device(0)
     n = a.size
     e = JacobiEngine(StencilSpec(dims=3, dtype=a.dtype), n, n, n, device=0)
