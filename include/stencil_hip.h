@@ -292,6 +292,25 @@ int stencil_sweepk_signal_gated(const stencil_layout* l, const void* in, void* o
                                 int32_t steps, uint32_t* counters, uint64_t* face_signal, uint32_t gate_need,
                                 uint32_t* release_flag, int32_t* signals_per_face, void* stream);
 int stencil_exchange_done(uint32_t* counters, uint32_t value, void* stream);
+/* The face-signalled launches that also report their update (the checking
+ * round of a face-signalled slab job, stencil_slab_run_until): `out`, the
+ * counters and the face signal are exactly stencil_sweepk_signal's (the gated
+ * form: stencil_sweepk_signal_gated's, halo gate included), and the launch
+ * raises *update_max_bits exactly as stencil_sweepk_update_max does -- the same
+ * per-cell condition (the store's own), up- and down-marching chunks alike, so
+ * the word is bit for bit that call's for the same range.  The 7-point star,
+ * r = 1, naive order, steps 3..5: other steps and a NULL word are
+ * STENCIL_EINVAL, other problems (the box included) STENCIL_EUNSUPPORTED.  A
+ * range shorter than `steps` planes is STENCIL_EINVAL here (such a launch
+ * signals one face only).  fp32 and fp64 steps = 4 run 6-row
+ * strips (the plain checking launch's remedy): the same sums, no scratch. */
+int stencil_sweepk_signal_update_max(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
+                                     int32_t steps, uint32_t* counters, uint64_t* face_signal,
+                                     uint64_t* update_max_bits, int32_t* signals_per_face, void* stream);
+int stencil_sweepk_signal_update_max_gated(const stencil_layout* l, const void* in, void* out, int64_t begin,
+                                           int64_t end, int32_t steps, uint32_t* counters, uint64_t* face_signal,
+                                           uint64_t* update_max_bits, uint32_t gate_need, uint32_t* release_flag,
+                                           int32_t* signals_per_face, void* stream);
 /* face signals: 8 bytes of HIP signal memory (hipExtMallocWithFlags,
  * hipMallocSignalMemory) holding a uint64 count */
 int stencil_face_signal_create(uint64_t** face_signal);
@@ -527,6 +546,43 @@ int stencil_slab_download(stencil_slab_job* job, void* host, int64_t host_row, i
  * shorter round); synchronous.  elapsed_ms: host wall time of the rounds,
  * all devices synchronised at both ends. */
 int stencil_slab_run(stencil_slab_job* job, uint32_t iterations, float* elapsed_ms);
+/* Sweeps until the update is small: stencil_iterate_until's stopping rule on a
+ * slab job.  Blocks of min(check_every, max_iterations - done) sweeps, each
+ * followed by the norm (STENCIL_NORM_MAX / STENCIL_NORM_L2) of u^n - u^(n-1)
+ * over the whole global interior; stops with *converged = 1 when norm <= tol,
+ * with 0 on a NaN norm or at the cap (a shorter last block is checked too);
+ * max_iterations = 0: 0 sweeps, not converged, norm +inf.  STENCIL_OK either
+ * way.  Afterwards the job is in the state stencil_slab_run(*iterations_done)
+ * would leave.
+ *   Check in the launch (max norm, rounds of K = 3..5 7-point strip launches,
+ * block >= K, STENCIL_UNTIL_FUSED not 0): block - K sweeps as stencil_slab_run
+ * issues them, then one checking round of K sweeps -- a face-signalled job's
+ * round with stencil_sweepk_signal_update_max (gated when the job is), every
+ * other two-grid job's boundary + interior round with
+ * stencil_sweepk_update_max -- raising one 8-byte word per slab, zeroed in
+ * stream order before the round and copied back after it; the norm is the
+ * maximum of the slabs' bit patterns (a NaN pattern wins).
+ *   Otherwise (L2, the box, blocks shorter than K, other families,
+ * STENCIL_UNTIL_FUSED=0): block - 1 sweeps, one round of a single sweep, then
+ * stencil_diff_norms' kernels per slab over its own planes; the maximum, or
+ * the per-plane sums added in ascending global plane order.  A plane's values
+ * depend on nx, ny and the row pitch alone, so both norms are bit for bit the
+ * single grid's.
+ *   Every host wait goes through the job's deadline (stencil_slab_set_timeout).
+ * STENCIL_EINVAL: NULL job, check_every = 0, tol < 0 or NaN, unknown norm.
+ * STENCIL_EUNSUPPORTED: STENCIL_SLAB_ROLLING jobs (one grid: u^(n-1) is gone)
+ * and rank-mode jobs (the check would need an all-reduce over the ranks).
+ * elapsed_ms: host wall time of rounds and checks, as stencil_slab_run.
+ * stencil_slab_until_plan (host only, no device): the rounds of one block of
+ * `block` sweeps, its checking round included -- fused (block-K)/K rounded up
+ * + 1, un-fused (block-1)/K rounded up + 1, K as stencil_plan resolves it --
+ * and whether the check rides in the launch.  STENCIL_EINVAL: block = 0,
+ * unknown norm, a problem that is not a valid slab global. */
+int stencil_slab_run_until(stencil_slab_job* job, uint32_t max_iterations, uint32_t check_every, int32_t norm,
+                           double tol, uint32_t* iterations_done, double* last_norm, int* converged,
+                           float* elapsed_ms);
+int stencil_slab_until_plan(const stencil_problem* global, uint32_t block, int32_t norm, int64_t* rounds,
+                            int32_t* fused_check);
 /* Per-plane interior sums of the current global grid (nz doubles, host). */
 int stencil_slab_plane_sums(stencil_slab_job* job, double* sums);
 /* Kernel timing for roofline figures: with timing on, every round records

@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "stencil_sweepk_signal_gated", "stencil_exchange_done", "stencil_slab_round_info", "stencil_pack_table",
     "stencil_slab_exchange_budget", "stencil_diff_norms", "stencil_iterate_until",
     "stencil_sweepk_update_max", "stencil_until_plan",
+    "stencil_sweepk_signal_update_max", "stencil_sweepk_signal_update_max_gated",
+    "stencil_slab_run_until", "stencil_slab_until_plan",
 )
 
 
@@ -116,7 +118,7 @@ def load(debug: bool | None = None) -> ctypes.CDLL:
             f"{path} is missing: the HIP extension has not been built "
             "(run `make` or `python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in signatures().items():
+    for name, (res, args) in {**signatures(), **slab_until_signatures()}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -181,6 +183,11 @@ def signatures() -> dict:
         "stencil_sweepk_signal_gated": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
                                                 c_uint32, c_void_p, POINTER(c_int32), c_void_p]),
         "stencil_exchange_done": (c_int, [c_void_p, c_uint32, c_void_p]),
+        "stencil_sweepk_signal_update_max": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                                     c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+        "stencil_sweepk_signal_update_max_gated": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                                           c_void_p, c_void_p, c_uint32, c_void_p, POINTER(c_int32),
+                                                           c_void_p]),
         "stencil_face_signal_create": (c_int, [POINTER(c_void_p)]),
         "stencil_face_signal_destroy": (c_int, [c_void_p]),
         "stencil_face_signal_reset": (c_int, [c_void_p, c_void_p]),
@@ -213,6 +220,17 @@ def signatures() -> dict:
                                                  POINTER(c_float)]),
         "stencil_slab_set_timeout": (c_int, [c_void_p, c_int64]),
         "stencil_slab_exchange_time": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), POINTER(c_int64)]),
+    }
+
+
+def slab_until_signatures() -> dict:
+    """The convergence-controlled slab entry points.  Kept apart from
+    signatures(): they exist in the product library only (the CPU fake device
+    of tests/cpu_slab/ binds every stencil_slab_* name signatures() lists)."""
+    return {
+        "stencil_slab_run_until": (c_int, [c_void_p, c_uint32, c_uint32, c_int32, c_double, POINTER(c_uint32),
+                                           POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
+        "stencil_slab_until_plan": (c_int, [POINTER(Problem), c_uint32, c_int32, POINTER(c_int64), POINTER(c_int32)]),
     }
 
 

@@ -660,6 +660,64 @@ int stencil_sweepk_signal_gated(const stencil_layout* l, const void* in, void* o
     return rc;
 }
 
+// The face-signalled launches that also report their update: the checks the
+// plain checking launch makes, then stencil_sweepk_signal's.  A range shorter
+// than `steps` planes would signal one face only: refused here.
+static int signal_update_max_args(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
+                                  int32_t steps, const uint32_t* counters, const uint64_t* update_max_bits) {
+    if (int rc = check_layout(l)) return rc;
+    if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 3..5 (got %d)", steps);
+    if (!temporal2_supports(l->prob))
+        return set_error(STENCIL_EUNSUPPORTED,
+                         "face-signalled update-max sweeps cover the 3D r=1 naive 7-point star only");
+    if (!counters) return set_error(STENCIL_EINVAL, "null counters");
+    if (!update_max_bits) return set_error(STENCIL_EINVAL, "null update_max_bits");
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
+    if (end - begin < steps)
+        return set_error(STENCIL_EINVAL, "a face-signalled range needs at least %d planes (got %lld)", steps,
+                         (long long)(end - begin));
+    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
+    return STENCIL_OK;
+}
+
+int stencil_sweepk_signal_update_max(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
+                                     int32_t steps, uint32_t* counters, uint64_t* face_signal,
+                                     uint64_t* update_max_bits, int32_t* signals_per_face, void* stream) {
+    if (int rc = signal_update_max_args(l, in, out, begin, end, steps, counters, update_max_bits)) return rc;
+    int nsig = 0;
+    const int rc = launch_tkstrip_signal_update_max(*l, in, out, begin, end, steps, counters,
+                                                    reinterpret_cast<unsigned long long*>(face_signal),
+                                                    reinterpret_cast<unsigned long long*>(update_max_bits), &nsig,
+                                                    as_stream(stream));
+    if (rc == STENCIL_OK) {
+        if (signals_per_face) *signals_per_face = nsig;
+        clear_error();
+    }
+    return rc;
+}
+
+int stencil_sweepk_signal_update_max_gated(const stencil_layout* l, const void* in, void* out, int64_t begin,
+                                           int64_t end, int32_t steps, uint32_t* counters, uint64_t* face_signal,
+                                           uint64_t* update_max_bits, uint32_t gate_need, uint32_t* release_flag,
+                                           int32_t* signals_per_face, void* stream) {
+    if (int rc = signal_update_max_args(l, in, out, begin, end, steps, counters, update_max_bits)) return rc;
+    int nsig = 0;
+    StripGate gate;
+    gate.word = counters + 3;
+    gate.release = release_flag;
+    gate.need = gate_need;
+    const int rc = launch_tkstrip_signal_update_max(*l, in, out, begin, end, steps, counters,
+                                                    reinterpret_cast<unsigned long long*>(face_signal),
+                                                    reinterpret_cast<unsigned long long*>(update_max_bits), &nsig,
+                                                    as_stream(stream), gate);
+    if (rc == STENCIL_OK) {
+        if (signals_per_face) *signals_per_face = nsig;
+        clear_error();
+    }
+    return rc;
+}
+
 int stencil_exchange_done(uint32_t* counters, uint32_t value, void* stream) {
     clear_error();
     if (!counters) return set_error(STENCIL_EINVAL, "null counters");
@@ -1111,7 +1169,9 @@ double scalar_norm(const double* host, int64_t n, int32_t norm) {
     return norm == STENCIL_NORM_MAX ? m : std::sqrt(s);
 }
 
-// stencil_iterate_until: the sweeps of the checking K-step launch
+}  // namespace
+
+// stencil_iterate_until (and stencil_slab_run_until, slab.hip): the sweeps of the checking K-step launch
 // (stencil_sweepk_update_max) that ends a block of `block` sweeps, or 0 when
 // the block keeps the un-fused check (single sweep + stencil_diff_norms): the
 // max norm on a job of K-step strip launches, blocks of at least K sweeps.
@@ -1124,7 +1184,6 @@ int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm) {
     return k > 0 && block >= uint32_t(k) ? k : 0;
 }
 
-}  // namespace
 }  // namespace stencil
 
 extern "C" {

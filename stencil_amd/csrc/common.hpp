@@ -201,6 +201,10 @@ struct StripGate {
     const uint32_t* word = nullptr;
     uint32_t* release = nullptr;
     uint32_t need = 0;
+    // a face-signalled launch that also reports its update
+    // (stencil_sweepk_signal_update_max): the word, which plain checking
+    // launches pass in the kernel's fsig argument
+    unsigned long long* umax = nullptr;
 };
 int launch_tkstrip_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                           unsigned* sig, unsigned long long* fsig, int* nsig, hipStream_t s,
@@ -210,6 +214,14 @@ int launch_tkstrip_signal(const stencil_layout& l, const void* in, void* out, in
 // they store (stencil_sweepk_update_max)
 int launch_tkstrip_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                               unsigned long long* word, hipStream_t s);
+// launch_tkstrip_signal's launches that also raise *word as launch_tkstrip_update_max does
+// (stencil_sweepk_signal_update_max)
+int launch_tkstrip_signal_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
+                                     int steps, unsigned* sig, unsigned long long* fsig, unsigned long long* word,
+                                     int* nsig, hipStream_t s, const StripGate& gate = StripGate{});
+// stencil_iterate_until's rule (api.hip): the sweeps of the checking K-step launch that ends a block of
+// `block` sweeps on problem `p`, or 0 when the block keeps the un-fused check
+int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm);
 int launch_boxk(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                 hipStream_t s);
 int launch_boxk_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,

@@ -86,6 +86,9 @@ void Stencil::initialize_matrix() {
 // the single-grid run: the rounds on grids already resident on the GPUs.
 template <class T>
 auto Stencil::run_slabs(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) -> std::chrono::steady_clock::duration {
+    if (options.dims != 3 && options.until())
+        throw std::runtime_error("--tol with --gpus > 1 / HIPMultiGPU needs a 3D grid: slab jobs split 3D grids along z "
+                                 "(use --dims 3)");
     if (options.dims != 3) throw std::runtime_error("--gpus / HIPMultiGPU split 3D grids along z (use --dims 3)");
     if (options.share_device && !options.exchange_copy)
         throw std::runtime_error("--share-device needs --exchange copy (RCCL takes one slab per GPU)");
@@ -116,14 +119,32 @@ auto Stencil::run_slabs(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) -> std
         int32_t k = 1;
         check(stencil_slab_info(job.j, 0, nullptr, nullptr, nullptr, &k), "stencil_slab_info");
         check(stencil_slab_run(job.j, uint32_t(std::min<int64_t>(options.iterations, k) + 1), nullptr), "slab warm-up");
+        // and, with --tol, one checked block (the checking round's kernels, the check's memory)
+        if (options.until())
+            check(stencil_slab_run_until(job.j, std::min(options.iterations, options.check_every), options.check_every,
+                                         options.norm_l2 ? STENCIL_NORM_L2 : STENCIL_NORM_MAX, 0.0, nullptr, nullptr,
+                                         nullptr, nullptr),
+                  "slab warm-up");
         check(stencil_slab_upload(job.j, matrix.data(), matrix.row_stride(), matrix.rows_with_boundary()), "slab upload");
     }
     float ms = 0.f;
     auto const start = std::chrono::steady_clock::now();
-    check(stencil_slab_run(job.j, options.iterations, &ms), "stencil_slab_run");
+    if (options.until()) {
+        // -i is the cap: sweep until one sweep's update is <= --tol
+        uint32_t done = 0;
+        int conv = 0;
+        check(stencil_slab_run_until(job.j, options.iterations, options.check_every,
+                                     options.norm_l2 ? STENCIL_NORM_L2 : STENCIL_NORM_MAX, options.tol, &done, &run_norm,
+                                     &conv, &ms),
+              "stencil_slab_run_until");
+        sweeps_done = done;
+        run_converged = conv != 0;
+    } else {
+        check(stencil_slab_run(job.j, options.iterations, &ms), "stencil_slab_run");
+    }
     auto const end = std::chrono::steady_clock::now();
     device_ms = ms;
-    BoundaryGrid<T>& dst = (options.iterations & 1u) ? result : matrix;  // parity rule, stencil.cpp:88-92,134
+    BoundaryGrid<T>& dst = (sweeps() & 1u) ? result : matrix;  // parity rule, stencil.cpp:88-92,134
     check(stencil_slab_download(job.j, dst.data(), dst.row_stride(), dst.rows_with_boundary()), "slab download");
     return end - start;
 }
@@ -134,12 +155,7 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     if (method == CPU) return run_cpu(matrix, result);
     initialize_matrix();
     const bool ref_variant = method == DMA || method == DMA_STATIC_UNROLL || method == DMA_SLAVE_PACK || method == RMA;
-    if (method == HIP_MULTI_GPU || (options.gpus > 1 && !ref_variant)) {
-        if (options.until())
-            throw std::runtime_error("--tol covers single-GPU runs only: a slab job (HIPMultiGPU, --gpus > 1) has no "
-                                     "convergence check");
-        return run_slabs(matrix, result);
-    }
+    if (method == HIP_MULTI_GPU || (options.gpus > 1 && !ref_variant)) return run_slabs(matrix, result);
 
     stencil_problem p{};
     p.dims = options.dims;

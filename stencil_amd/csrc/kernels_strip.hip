@@ -273,6 +273,13 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // 64-bit atomic max of the bit pattern: non-negative doubles order as
 // unsigned integers and NaN patterns sort above +inf, so the word is the same
 // whatever order the workgroups arrive in, and a NaN stays.
+// SIG + UMAX (stencil_sweepk_signal_update_max): a face-signalled launch needs
+// `fsig` for itself, so its word travels in the gate argument (StripGate::umax).
+// Up- and down-marching chunks count alike: the accumulator lives outside the
+// segments, and stage K's centre operand is t_{K-1}(p-K) of the plane stored
+// whichever way the chunk is walked.  The face adds touch no LDS and their
+// barrier is workgroup-uniform, so the reduction below (behind a barrier of
+// its own) still finds the boundary rows free.
 template <typename T, int V, int RY, int NW, int K, bool DB, int DIAG = 0, bool SIG = false, int NS = 4, bool FP = true,
           bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false>
 __global__ void __launch_bounds__(64 * NW)
@@ -285,8 +292,8 @@ __global__ void __launch_bounds__(64 * NW)
     constexpr int XR = Tl::XR, TX = Tl::TX, TY = Tl::TY, RH = Tl::RH, RW = Tl::RW, NB = Tl::NB;
     constexpr int LW = Tl::LW, NSTR = Tl::NSTR;
     static_assert(!SPLIT || !TIER, "SPLIT: plain or face-signalled launches");
-    static_assert(!UMAX || (!TIER && !SIG && DIAG == 0 && !TK_SST && !TK_XRING8 && !TK_PROBE_NOBAR),
-                  "UMAX: plain launches of the product shapes only");
+    static_assert(!UMAX || (!TIER && DIAG == 0 && !TK_SST && !TK_XRING8 && !TK_PROBE_NOBAR),
+                  "UMAX: plain or face-signalled launches of the product shapes only");
     constexpr bool SST = Tl::SSTS && !SIG && !TIER && !HL;
     constexpr int NI = (RY + 1) / 2;  // SST: row pairs per strip
     typedef T V4T __attribute__((ext_vector_type(4)));
@@ -867,9 +874,10 @@ __global__ void __launch_bounds__(64 * NW)
         __syncthreads();
         if (threadIdx.x == 0 && threadIdx.y == 0) {
             for (int i = 1; i < NW; ++i) m = red[i] > m ? red[i] : m;
+            unsigned long long* const word = SIG ? gate.umax : fsig;
             // a word already at least as large needs no atomic (a stale load only costs one)
-            if (m > __hip_atomic_load(fsig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                __hip_atomic_fetch_max(fsig, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (m > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                __hip_atomic_fetch_max(word, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -1680,6 +1688,40 @@ int launch_tkstrip_update_max(const stencil_layout& l, const void* in, void* out
         }
     }
     return set_error(STENCIL_EINVAL, "update-max sweeps: steps must be 3, 4 or 5 (got %d)", steps);
+}
+
+// The face-signalled default shapes that also report their update
+// (stencil_sweepk_signal_update_max; SIG + UMAX above): launch_tkstrip_signal's
+// launches with the word in gate.umax.  fp32 K = 4 runs 6-row strips, as the
+// plain checking launch does (the 7-row shape has no VGPR left for the
+// accumulator).  DESIGN.md §5.6 has the resource table.
+int launch_tkstrip_signal_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
+                                     int steps, unsigned* sig, unsigned long long* fsig, unsigned long long* word,
+                                     int* nsig, hipStream_t s, const StripGate& gate_in) {
+    if (!temporal2_supports(l.prob))
+        return set_error(STENCIL_EUNSUPPORTED, "face-signalled update-max sweeps cover the 3D r=1 naive 7-point star only");
+    if (!word) return set_error(STENCIL_EINVAL, "null update_max_bits");
+    StripGate gate = gate_in;
+    gate.umax = word;
+    constexpr bool U = true;
+    if (l.prob.dtype == STENCIL_F32) {
+        switch (steps) {
+        case 3: return launch_st<float, 4, 4, 8, 3, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
+        case 4: return launch_st<float, 2, 6, 8, 4, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
+        case 5: return launch_st<float, 2, 5, 8, 5, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
+        default: break;
+        }
+    } else {
+        switch (steps) {
+        case 3: return launch_st<double, 2, 4, 8, 3, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
+        // 6-row strips here too: the plain signalled 7-row shape already spills (52 B of scratch per lane),
+        // with the accumulator 80 B; 6 rows take none.  Bitwise the same sweep (64 x 40 tiles).
+        case 4: return launch_st<double, 1, 6, 8, 4, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
+        case 5: return launch_st<double, 1, 5, 8, 5, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
+        default: break;
+        }
+    }
+    return set_error(STENCIL_EINVAL, "face-signalled update-max sweeps: steps must be 3, 4 or 5 (got %d)", steps);
 }
 
 #endif  // STRIP_ILP_TU

@@ -26,6 +26,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -394,6 +395,58 @@ struct HipDev {
         *nsig = n;
         return rc;
     }
+    // ---- convergence checks (slab_core.hpp run_until) ----
+    static int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm) {
+        return stencil::until_fused_steps(p, block, norm);
+    }
+    // A slab's check memory: device = the update word (8 bytes) and, from
+    // `norm_offset` on, the norm kernels' workspace for n planes; host = its
+    // pinned landing (the word, then n maxima and n sums), so that the copies
+    // back are asynchronous and the host waits for them with the job's deadline
+    static int check_alloc(const stencil_layout& l, int64_t n, size_t norm_offset, void** dev, void** host) {
+        *dev = *host = nullptr;
+        if (int rc = alloc(int64_t(norm_offset) + diff_norms_workspace_bytes(l, n), dev)) return rc;
+        if (hipHostMalloc(host, sizeof(uint64_t) + size_t(2 * n) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(*dev);
+            *dev = *host = nullptr;
+            return set_error(STENCIL_ENOMEM, "pinned host memory for a slab's check");
+        }
+        return STENCIL_OK;
+    }
+    static int word_zero(void* word, Stream s) {
+        STENCIL_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(uint64_t), s));
+        return STENCIL_OK;
+    }
+    static int to_host(void* host, const void* dev, size_t bytes, Stream s) {
+        STENCIL_HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+        return STENCIL_OK;
+    }
+    static int sweepk_update_max(const stencil_layout* l, const void* src, void* dst, int64_t b, int64_t e, int k,
+                                 uint64_t* word, Stream s) {
+        return stencil_sweepk_update_max(l, src, dst, b, e, k, word, s);
+    }
+    static int sweepk_signal_update_max(const stencil_layout* l, const void* src, void* dst, int64_t b, int64_t e, int k,
+                                        uint32_t* counters, uint64_t* fsig, uint64_t* word, int* nsig, Stream s) {
+        int32_t n = 0;
+        const int rc = stencil_sweepk_signal_update_max(l, src, dst, b, e, k, counters, fsig, word, &n, s);
+        *nsig = n;
+        return rc;
+    }
+    static int sweepk_signal_update_max_gated(const stencil_layout* l, const void* src, void* dst, int64_t b, int64_t e,
+                                              int k, uint32_t* counters, uint64_t* fsig, uint64_t* word, uint32_t need,
+                                              uint32_t* release, int* nsig, Stream s) {
+        int32_t n = 0;
+        if (knob("STENCIL_SLAB_GATE_SKIP", 0)) need = 0;  // as sweepk_signal_gated
+        const int rc =
+            stencil_sweepk_signal_update_max_gated(l, src, dst, b, e, k, counters, fsig, word, need, release, &n, s);
+        *nsig = n;
+        return rc;
+    }
+    static int diff_norms(const stencil_layout* l, const void* a, const void* b, int64_t begin, int64_t end,
+                          double* workspace, Stream s) {
+        return launch_diff_norms(*l, a, b, begin, end, workspace, s);
+    }
     static int exchange_done(uint32_t* counters, uint32_t value, Stream s) {
         return stencil_exchange_done(counters, value, s);
     }
@@ -582,6 +635,33 @@ int stencil_slab_upload(stencil_slab_job* job, const void* host, int64_t host_ro
 int stencil_slab_run(stencil_slab_job* job, uint32_t iterations, float* elapsed_ms) {
     const stencil::SustainedScope sustained(iterations >= stencil::kSustainedSweeps);
     return core::run<HipDev>(job, iterations, elapsed_ms);
+}
+
+int stencil_slab_run_until(stencil_slab_job* job, uint32_t max_iterations, uint32_t check_every, int32_t norm,
+                           double tol, uint32_t* iterations_done, double* last_norm, int* converged,
+                           float* elapsed_ms) {
+    const stencil::SustainedScope sustained(max_iterations >= stencil::kSustainedSweeps);
+    return core::run_until<HipDev>(job, max_iterations, check_every, norm, tol, iterations_done, last_norm, converged,
+                                   elapsed_ms);
+}
+
+int stencil_slab_until_plan(const stencil_problem* global, uint32_t block, int32_t norm, int64_t* rounds,
+                            int32_t* fused_check) {
+    using stencil::set_error;
+    if (!global) return set_error(STENCIL_EINVAL, "null problem");
+    if (block == 0) return set_error(STENCIL_EINVAL, "block must be at least 1");
+    if (norm != STENCIL_NORM_MAX && norm != STENCIL_NORM_L2) return set_error(STENCIL_EINVAL, "bad norm %d", norm);
+    stencil_problem g;
+    if (core::check_global<HipDev>(global, &g, 0) != STENCIL_OK) {
+        const std::string why = stencil_last_error_message();
+        return set_error(STENCIL_EINVAL, "not a slab job's global problem: %s", why.c_str());
+    }
+    const int k = HipDev::fuse_depth(g);
+    const int kf = core::check_steps<HipDev>(g, k, block, norm);
+    if (rounds) *rounds = core::until_rounds(block, k, kf != 0);
+    if (fused_check) *fused_check = kf ? 1 : 0;
+    stencil::clear_error();
+    return STENCIL_OK;
 }
 
 int stencil_slab_download(stencil_slab_job* job, void* host, int64_t host_row, int64_t host_rows) {

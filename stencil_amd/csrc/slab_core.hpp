@@ -41,9 +41,11 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -110,6 +112,15 @@ struct Slab {
     // and the chosen pair's ms per K-step launch
     int placements = 1;
     float placement_ms = 0.f;
+    // convergence checks (run_until; allocated by its first call,
+    // Dev::check_alloc): device memory whose first 8 bytes are the checking
+    // launches' update word and whose doubles from byte 256 on are the norm
+    // kernels' workspace for this slab's n planes; its pinned host landing
+    // (the word, then 2n doubles); the event that orders the word's zeroing
+    // on A before the checking launch on B
+    void* chk_dev = nullptr;
+    void* chk_host = nullptr;
+    typename Dev::Event ev_word{};
 };
 
 template <class Dev>
@@ -368,11 +379,33 @@ int exchange(Job<Dev>& j, int pos, Pre&& pre = Pre{}) {
 }
 
 // ---- rounds ---------------------------------------------------------------
+// The launches of a round are a policy, so that a checking round (run_until)
+// is the same round with launches that also raise the slab's update word.
+// The policies below are the plain launches; the checking ones (further down)
+// use Dev members only HipDev has, and are instantiated by run_until alone.
+template <class Dev>
+struct PlainSweep {
+    int begin(Slab<Dev>&) const { return STENCIL_OK; }
+    int operator()(Slab<Dev>& s, const void* src, void* dst, int64_t b, int64_t e, int k,
+                   typename Dev::Stream st) const {
+        return Dev::sweepk(&s.l, src, dst, b, e, k, st);
+    }
+};
+template <class Dev>
+struct PlainSignal {
+    int begin(Slab<Dev>&) const { return STENCIL_OK; }
+    int operator()(const Job<Dev>& j, Slab<Dev>& s, const void* src, void* dst, int k, int* nsig) const {
+        if (j.gate)
+            return Dev::sweepk_signal_gated(&s.l, src, dst, 0, s.n, k, s.counters, s.fsig, s.xseq, s.tflag, nsig, s.sb);
+        return Dev::sweepk_signal(&s.l, src, dst, 0, s.n, k, s.counters, s.fsig, nsig, s.sb);
+    }
+};
+
 // One round of `k` fused sweeps: src -> dst on every slab, then the exchange
 // of dst's faces.  Boundary planes on A (the exchange queued behind them),
 // the interior on B.
-template <class Dev>
-int slab_round(Job<Dev>& j, int k) {
+template <class Dev, class Sweep = PlainSweep<Dev>>
+int slab_round(Job<Dev>& j, int k, const Sweep& sweep = Sweep{}) {
     const int src_pos = cur_pos(j), dst_pos = 1 - src_pos;
     const int64_t edge = j.depth;
     for (size_t i = 0; i < j.s.size(); ++i) {
@@ -386,20 +419,21 @@ int slab_round(Job<Dev>& j, int k) {
             SLAB_TRY(Dev::stream_wait(s.sb, s.ev_bnd));
             SLAB_TRY(Dev::stream_wait(s.sa, s.ev_int));
         }
+        SLAB_TRY(sweep.begin(s));
         const int64_t plane_cells = s.l.prob.nx * s.l.prob.ny;
         // serial rounds: the whole slab in one launch on A, the exchange
         // behind it -- nothing runs beside the launch (an overlapped exchange's
         // copy or RCCL kernels take CUs the one-per-CU strip grid counts on)
         if (!j.serial && s.n > 2 * edge) {
             SLAB_TRY(time_begin(j, i, s.sb));
-            SLAB_TRY(Dev::sweepk(&s.l, src, dst, edge, s.n - edge, k, s.sb));
+            SLAB_TRY(sweep(s, src, dst, edge, s.n - edge, k, s.sb));
             SLAB_TRY(time_end(j, i, s.sb, plane_cells * (s.n - 2 * edge), 1));
             SLAB_TRY(Dev::event_record(s.ev_int, s.sb));
-            SLAB_TRY(Dev::sweepk(&s.l, src, dst, 0, edge, k, s.sa));
-            SLAB_TRY(Dev::sweepk(&s.l, src, dst, s.n - edge, s.n, k, s.sa));
+            SLAB_TRY(sweep(s, src, dst, 0, edge, k, s.sa));
+            SLAB_TRY(sweep(s, src, dst, s.n - edge, s.n, k, s.sa));
         } else {
             SLAB_TRY(time_begin(j, i, s.sa));
-            SLAB_TRY(Dev::sweepk(&s.l, src, dst, 0, s.n, k, s.sa));
+            SLAB_TRY(sweep(s, src, dst, 0, s.n, k, s.sa));
             SLAB_TRY(time_end(j, i, s.sa, plane_cells * s.n, 1));
             SLAB_TRY(Dev::event_record(s.ev_int, s.sa));
         }
@@ -425,8 +459,8 @@ int slab_round(Job<Dev>& j, int k) {
 // exchange(r-1) received (B waits for A); exchange(r) receives into the halo
 // planes launch(r-1) read, and starts only once launch(r) has signalled,
 // i.e. after launch(r-1) ended (one stream).
-template <class Dev>
-int slab_round_signal(Job<Dev>& j, int k) {
+template <class Dev, class Launch = PlainSignal<Dev>>
+int slab_round_signal(Job<Dev>& j, int k, const Launch& launch = Launch{}) {
     const int src_pos = cur_pos(j), dst_pos = 1 - src_pos;
     for (size_t i = 0; i < j.s.size(); ++i) {
         Slab<Dev>& s = j.s[i];
@@ -443,12 +477,9 @@ int slab_round_signal(Job<Dev>& j, int k) {
         // costs a third queue hop per round: ~20 us of 500 at 512^3)
         if (j.chained && !(j.gate && j.gate_chain)) SLAB_TRY(Dev::stream_wait(s.sb, s.ev_xout));
         int nsig = 0;
+        SLAB_TRY(launch.begin(s));
         SLAB_TRY(time_begin(j, i, s.sb));
-        if (j.gate)
-            SLAB_TRY(Dev::sweepk_signal_gated(&s.l, src, dst, 0, s.n, k, s.counters, s.fsig, s.xseq, s.tflag, &nsig,
-                                              s.sb));
-        else
-            SLAB_TRY(Dev::sweepk_signal(&s.l, src, dst, 0, s.n, k, s.counters, s.fsig, &nsig, s.sb));
+        SLAB_TRY(launch(j, s, src, dst, k, &nsig));
         SLAB_TRY(time_end(j, i, s.sb, s.l.prob.nx * s.l.prob.ny * s.n, 1));
         SLAB_TRY(Dev::event_record(s.ev_int, s.sb));
         s.sig_target += uint32_t(nsig);
@@ -824,11 +855,13 @@ void release(JobT* j) {
         (void)Dev::set_device(s.device);
         if (s.comm) Dev::comm_destroy(s.comm);
         if (!drained) continue;
-        for (void* p : {s.a, s.b, s.xs, s.xr})
+        for (void* p : {s.a, s.b, s.xs, s.xr, s.chk_dev})
             if (p) Dev::free(p);
+        if (s.chk_host) Dev::free_flag(static_cast<uint32_t*>(s.chk_host));  // pinned host memory, as the flag
         for (typename Dev::Stream st : {s.sx, s.sa, s.sb, s.sx_alt, s.sb_alt})
             if (st) Dev::stream_destroy(st);
-        for (typename Dev::Event e : {s.ev_bnd, s.ev_int, s.ev_join, s.ev_xin, s.ev_xout, s.tb0, s.tb1, s.tx0, s.tx1, s.tr0})
+        for (typename Dev::Event e : {s.ev_bnd, s.ev_int, s.ev_join, s.ev_xin, s.ev_xout, s.tb0, s.tb1, s.tx0, s.tx1, s.tr0,
+                                      s.ev_word})
             if (e) Dev::event_destroy(e);
         for (typename Dev::Event e : s.ring)
             if (e) Dev::event_destroy(e);
@@ -1417,6 +1450,189 @@ int run(JobT* job, uint32_t iterations, float* elapsed_ms) {
     if (job->signal) SLAB_FAIL(*job, check_signal_timeouts(*job));
     const auto t1 = std::chrono::steady_clock::now();
     if (elapsed_ms) *elapsed_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    clear_error();
+    return STENCIL_OK;
+}
+
+// ---- convergence-controlled runs (stencil_slab_run_until) -------------------
+// stencil_iterate_until's stopping rule over the slabs of a two-grid job
+// (DESIGN.md §5.6).  Everything below uses Dev members only HipDev has
+// (check_alloc, word_zero, to_host, the update-max launches, diff_norms,
+// until_fused_steps): it is instantiated by slab.hip alone, never by the CPU
+// test build.
+constexpr size_t kCheckNormOffset = 256;  // Slab::chk_dev: the norm workspace behind the word
+
+// The checking launches of a boundary + interior / serial round: the word is
+// zeroed on A, B follows that through ev_word, and the round's two or three
+// launches accumulate into it.
+template <class Dev>
+struct CheckSweep {
+    int begin(Slab<Dev>& s) const {
+        if (int rc = Dev::word_zero(s.chk_dev, s.sa)) return rc;
+        if (int rc = Dev::event_record(s.ev_word, s.sa)) return rc;
+        return Dev::stream_wait(s.sb, s.ev_word);
+    }
+    int operator()(Slab<Dev>& s, const void* src, void* dst, int64_t b, int64_t e, int k,
+                   typename Dev::Stream st) const {
+        return Dev::sweepk_update_max(&s.l, src, dst, b, e, k, static_cast<uint64_t*>(s.chk_dev), st);
+    }
+};
+// The checking launch of a face-signalled round: one launch on B, the word
+// zeroed in front of it there.
+template <class Dev>
+struct CheckSignal {
+    int begin(Slab<Dev>& s) const { return Dev::word_zero(s.chk_dev, s.sb); }
+    int operator()(const Job<Dev>& j, Slab<Dev>& s, const void* src, void* dst, int k, int* nsig) const {
+        uint64_t* word = static_cast<uint64_t*>(s.chk_dev);
+        if (j.gate)
+            return Dev::sweepk_signal_update_max_gated(&s.l, src, dst, 0, s.n, k, s.counters, s.fsig, word, s.xseq,
+                                                       s.tflag, nsig, s.sb);
+        return Dev::sweepk_signal_update_max(&s.l, src, dst, 0, s.n, k, s.counters, s.fsig, word, nsig, s.sb);
+    }
+};
+
+// The sweeps of the checking round that ends a block of `block` sweeps on a
+// job of `k`-sweep rounds over `g`, or 0 when the block keeps the un-fused
+// check: until_fused_steps' rule on the global problem, on jobs whose rounds
+// are K-step 7-point strip launches.
+template <class Dev>
+int check_steps(const stencil_problem& g, int k, uint32_t block, int32_t norm) {
+    if (g.shape != STENCIL_STAR || k < 3 || k > 5) return 0;
+    return Dev::until_fused_steps(g, block, norm) == k ? k : 0;
+}
+
+// Rounds of one block of `block` sweeps, its checking round included.
+inline int64_t until_rounds(uint32_t block, int k, bool fused) {
+    const int64_t before = fused ? int64_t(block) - k : int64_t(block) - 1;
+    return before / k + (before % k ? 1 : 0) + 1;
+}
+
+// `sweeps` sweeps exactly as run() issues them: full rounds, then one shorter round.
+template <class Dev>
+int plain_rounds(Job<Dev>& j, uint32_t sweeps) {
+    uint32_t done = 0;
+    const uint32_t k = uint32_t(j.k);
+    for (; done + k <= sweeps; done += k) SLAB_TRY(one_round(j, int(k), true));
+    if (done < sweeps) SLAB_TRY(one_round(j, int(sweeps - done), false));
+    return STENCIL_OK;
+}
+
+// One checking round of K sweeps: the job's face-signalled round with the
+// checking launch, or slab_round's form with checking launches (a staged job
+// leaves its staged form here, as it does for remainder rounds).
+// A job whose exchange waits on a HIP signal word in the command processor
+// (STENCIL_SLAB_CPWAIT=1) also takes slab_round's form: the kernel finds the
+// add that completes a face by the running count modulo the launch's tiles, and
+// the K = 4 checking launches (6-row strips) have more tiles than the job's own
+// launches on planes of more than one tile row -- a face signal would then
+// never rise, and that wait has no timeout.
+template <class Dev>
+int check_round(Job<Dev>& j, int k) {
+    SLAB_TRY(throttle(j));
+    const bool signalled = j.signal && !j.s[0].fsig;
+    if (!signalled) j.gate_chain = false;  // only a gated launch may follow a gated launch unsynchronised
+    if (signalled)
+        SLAB_FAIL(j, slab_round_signal(j, k, CheckSignal<Dev>{}));
+    else
+        SLAB_FAIL(j, slab_round(j, k, CheckSweep<Dev>{}));
+    SLAB_FAIL(j, mark_round(j));
+    return STENCIL_OK;
+}
+
+template <class Dev, class JobT>
+int run_until(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t norm, double tol,
+              uint32_t* iterations_done, double* last_norm, int* converged, float* elapsed_ms) {
+    if (!job) return set_error(STENCIL_EINVAL, "null job");
+    if (check_every == 0) return set_error(STENCIL_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0.0)) return set_error(STENCIL_EINVAL, "tol must be a number >= 0");
+    if (norm != STENCIL_NORM_MAX && norm != STENCIL_NORM_L2) return set_error(STENCIL_EINVAL, "bad norm %d", norm);
+    if (job->margin)
+        return set_error(STENCIL_EUNSUPPORTED, "rolling slab jobs keep one grid: the previous sweep, which the check "
+                         "compares with, is gone");
+    if (job->nranks)
+        return set_error(STENCIL_EUNSUPPORTED, "rank-mode slab jobs: the check needs an all-reduce over the ranks, "
+                         "which is not built");
+    SLAB_TRY(sync_bounded(*job));
+    for (Slab<Dev>& s : job->s) {
+        if (s.chk_dev && s.ev_word) continue;
+        SLAB_TRY(Dev::set_device(s.device));
+        if (!s.chk_dev) SLAB_TRY(Dev::check_alloc(s.l, s.n, kCheckNormOffset, &s.chk_dev, &s.chk_host));
+        if (!s.ev_word) SLAB_TRY(Dev::event_create(&s.ev_word, false));
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    uint32_t done = 0;
+    int conv = 0;
+    double last = std::numeric_limits<double>::infinity();
+    std::vector<double> planes;  // un-fused: the global per-plane maxima, then the per-plane sums
+    while (done < max_iterations) {
+        const uint32_t block = std::min(check_every, max_iterations - done);
+        const int kf = check_steps<Dev>(job->global, job->k, block, norm);
+        if (kf) {
+            SLAB_TRY(plain_rounds(*job, block - uint32_t(kf)));
+            SLAB_TRY(check_round(*job, kf));
+            for (Slab<Dev>& s : job->s) {
+                SLAB_FAIL(*job, Dev::set_device(s.device));
+                SLAB_FAIL(*job, Dev::stream_wait(s.sa, s.ev_int));  // A behind the round's last checking launch
+                SLAB_FAIL(*job, Dev::to_host(s.chk_host, s.chk_dev, sizeof(uint64_t), s.sa));
+            }
+        } else {
+            SLAB_TRY(plain_rounds(*job, block - 1));
+            SLAB_TRY(one_round(*job, 1, false));
+            // the two grids now hold u^n and u^(n-1) on every slab's own planes
+            for (Slab<Dev>& s : job->s) {
+                SLAB_FAIL(*job, Dev::set_device(s.device));
+                SLAB_FAIL(*job, Dev::stream_wait(s.sa, s.ev_int));
+                double* ws = reinterpret_cast<double*>(static_cast<char*>(s.chk_dev) + kCheckNormOffset);
+                SLAB_FAIL(*job, Dev::diff_norms(&s.l, cur_grid(*job, s), grid_at(*job, s, 1 - cur_pos(*job)), 0, s.n, ws,
+                                                s.sa));
+                SLAB_FAIL(*job, Dev::to_host(static_cast<char*>(s.chk_host) + sizeof(uint64_t), ws,
+                                             size_t(2 * s.n) * sizeof(double), s.sa));
+            }
+        }
+        done += block;
+        SLAB_TRY(sync_bounded(*job));
+        if (job->signal) SLAB_FAIL(*job, check_signal_timeouts(*job));
+        if (kf) {
+            // the maximum of the slabs' bit patterns: non-negative doubles order as
+            // unsigned integers, NaN patterns above +inf's
+            uint64_t bits = 0;
+            for (const Slab<Dev>& s : job->s) {
+                uint64_t b = 0;
+                std::memcpy(&b, s.chk_host, sizeof b);
+                bits = std::max(bits, b);
+            }
+            std::memcpy(&last, &bits, sizeof last);
+            if (last != last) last = nan;
+        } else {
+            // stencil_iterate_until's scalar_norm over the global planes in ascending order
+            const int64_t nz = job->global.nz;
+            planes.assign(size_t(2 * nz), 0.0);
+            for (const Slab<Dev>& s : job->s) {
+                const char* h = static_cast<const char*>(s.chk_host) + sizeof(uint64_t);
+                std::memcpy(&planes[size_t(s.first)], h, size_t(s.n) * sizeof(double));
+                std::memcpy(&planes[size_t(nz + s.first)], h + size_t(s.n) * sizeof(double), size_t(s.n) * sizeof(double));
+            }
+            double m = 0.0, sum = 0.0;
+            bool any_nan = false;
+            for (int64_t u = 0; u < nz; ++u) {
+                any_nan = any_nan || planes[size_t(u)] != planes[size_t(u)];
+                m = std::max(m, planes[size_t(u)]);
+                sum += planes[size_t(nz + u)];
+            }
+            last = any_nan ? nan : (norm == STENCIL_NORM_MAX ? m : std::sqrt(sum));
+        }
+        if (last <= tol) {
+            conv = 1;
+            break;
+        }
+        if (last != last) break;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    if (elapsed_ms) *elapsed_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    if (iterations_done) *iterations_done = done;
+    if (last_norm) *last_norm = last;
+    if (converged) *converged = conv;
     clear_error();
     return STENCIL_OK;
 }

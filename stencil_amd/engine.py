@@ -231,6 +231,33 @@ class JacobiEngine:
                                                   ctypes.byref(n), _stream_handle(stream)), "stencil_sweepk_signal", lib=self.lib)
         return int(n.value)
 
+    def sweepk_signal_update_max(self, src: torch.Tensor, dst: torch.Tensor, begin: int, end: int, steps: int,
+                                 counters: torch.Tensor, stream=None, face_signal: "FaceSignal | None" = None,
+                                 gate_need: int | None = None, start_bits: int = 0):
+        """sweepk_signal over [begin, end) (3D 7-point star, steps 3..5) as the
+        launch that also reports its last sweep's update
+        (stencil_sweepk_signal_update_max; with gate_need the halo-gated form,
+        the gate word being counters[3]).  Returns (adds per face, the word as
+        sweepk_update_max returns it).  start_bits: the word's bit pattern
+        before the launch (0: a fresh word)."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(s):
+            word = torch.full((1,), int(np.array([start_bits], dtype=np.uint64).view(np.int64)[0]), dtype=torch.int64,
+                              device=self.device)
+        n = ctypes.c_int32(0)
+        fs = face_signal.ptr if face_signal is not None else None
+        args = (ctypes.byref(self.layout), ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), begin, end,
+                steps, ctypes.c_void_p(counters.data_ptr()), fs, ctypes.c_void_p(word.data_ptr()))
+        if gate_need is None:
+            _lib.check(self.lib.stencil_sweepk_signal_update_max(*args, ctypes.byref(n), _stream_handle(s)),
+                       "stencil_sweepk_signal_update_max", lib=self.lib)
+        else:
+            _lib.check(self.lib.stencil_sweepk_signal_update_max_gated(*args, gate_need, None, ctypes.byref(n),
+                                                                       _stream_handle(s)),
+                       "stencil_sweepk_signal_update_max_gated", lib=self.lib)
+        s.synchronize()
+        return int(n.value), float(np.array([int(word.item())], dtype=np.int64).view(np.float64)[0])
+
     def face_signal(self) -> "FaceSignal":
         return FaceSignal()
 
@@ -361,7 +388,7 @@ class JacobiEngine:
 @dataclass(frozen=True)
 class UntilResult:
     """What JacobiEngine.iterate_until returns."""
-    grid: torch.Tensor        # the grid that holds the last sweep
+    grid: torch.Tensor        # the grid that holds the last sweep (SlabJob.run_until: None, see download())
     iterations: int           # sweeps done
     converged: bool           # norm <= tol at the last check
     norm: float               # the last check's norm (+inf when nothing ran)
@@ -589,6 +616,26 @@ class SlabJob:
         _lib.check(self.lib.stencil_slab_run(self.job, iterations, ctypes.byref(ms)), "stencil_slab_run", lib=self.lib)
         return float(ms.value)
 
+    def run_until(self, tol: float, max_iterations: int, check_every: int = 100, norm: str = "max") -> "UntilResult":
+        """Sweep until the norm of one sweep's update over the whole global
+        interior is <= tol, checked every `check_every` sweeps and after the
+        last one, at most `max_iterations` sweeps (stencil_slab_run_until:
+        iterate_until's stopping rule on the slabs).  `grid` of the result is
+        None: download() gives the grid; `ms` is the host wall time."""
+        done, conv = ctypes.c_uint32(0), ctypes.c_int(0)
+        last, ms = ctypes.c_double(0.0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_slab_run_until(self.job, max_iterations, check_every, _lib.NORM_NAMES[norm], tol,
+                                                   ctypes.byref(done), ctypes.byref(last), ctypes.byref(conv),
+                                                   ctypes.byref(ms)), "stencil_slab_run_until", lib=self.lib)
+        return UntilResult(None, int(done.value), bool(conv.value), float(last.value), float(ms.value))
+
+    def until_plan(self, block: int, norm: str = "max") -> dict:
+        """One block of `block` sweeps of run_until (stencil_slab_until_plan,
+        host only): its rounds, the checking round included, and whether the
+        check rides in that round's launches."""
+        nx, ny, nz = self.shape
+        return slab_until_plan(self.spec, nx, ny, nz, block, norm, lib=self.lib)
+
     def kernel_timing(self, enable: bool) -> None:
         """Record hipEvents around slab 0's compute launch of every round from
         now on (the whole slab in face-signalled rounds, else its interior)."""
@@ -646,3 +693,14 @@ class SlabJob:
         _lib.check(self.lib.stencil_slab_plane_sums(self.job, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "stencil_slab_plane_sums", lib=self.lib)
         return out
+
+
+def slab_until_plan(spec: StencilSpec, nx: int, ny: int, nz: int, block: int, norm: str = "max", lib=None) -> dict:
+    """stencil_slab_until_plan for the global problem (host only, no job and
+    no device needed): {"rounds", "fused_check"}."""
+    lib = lib if lib is not None else _lib.load()
+    prob = spec.problem(nx, ny, nz)
+    rounds, fused = ctypes.c_int64(0), ctypes.c_int32(0)
+    _lib.check(lib.stencil_slab_until_plan(ctypes.byref(prob), block, _lib.NORM_NAMES[norm], ctypes.byref(rounds),
+                                           ctypes.byref(fused)), "stencil_slab_until_plan", lib=lib)
+    return {"rounds": int(rounds.value), "fused_check": bool(fused.value)}

@@ -23,6 +23,17 @@ libstencil_hip.so, e.g. the parent commit's -- each in a fresh child process,
 the arms alternating, `--rounds` children per arm.  Every child also times the
 checking launch against the plain launch of the same shape, interleaved.
 --nx/--ny/--nz give a grid that is not a cube; --launch-only skips the jobs.
+
+    python tools/norm_bench.py --slab-ab [--rounds 3] [--parent-lib PATH] [--out FILE]
+
+The same protocol for stencil_slab_run_until on a one-slab
+PERIODIC job (the interior-rank rehearsal): per child SlabJob.run(sweeps) and
+run_until with a tol it never meets, a check every 100, 20 and 4 sweeps, host
+wall time of each; arms: the check in the launch, STENCIL_UNTIL_FUSED=0, the
+same two on a boundary + interior job (STENCIL_SLAB_SIGNAL=0: its checking
+rounds are slab_round's form), and -- with --parent-lib -- run() alone on
+another build.  Every child of this build also times the face-signalled checking
+launch against the plain face-signalled launch, between events.
 """
 import argparse
 import ctypes
@@ -36,7 +47,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from stencil_amd import _lib
-from stencil_amd.engine import JacobiEngine, StencilSpec, _stream_handle
+from stencil_amd.engine import JacobiEngine, SlabJob, StencilSpec, _stream_handle
 
 
 EVERY = (100, 20, 4)
@@ -107,6 +118,127 @@ def child(a):
     print(json.dumps(out))
 
 
+def slab_child(a):
+    """One arm of --slab-ab in this (fresh) process.  Prints one JSON line."""
+    if a.lib:
+        _lib.LIB_PATH = a.lib
+        probe, sigs, more = ctypes.CDLL(a.lib), _lib.signatures(), _lib.slab_until_signatures()
+        _lib.signatures = lambda: {k: v for k, v in sigs.items() if hasattr(probe, k)}
+        _lib.slab_until_signatures = lambda: {k: v for k, v in more.items() if hasattr(probe, k)}
+    torch.cuda.set_device(0)
+    nx, ny, nz = a.nx or a.size, a.ny or a.size, a.nz or a.size
+    job = SlabJob(StencilSpec(dims=3, dtype=a.dtype), nx, ny, nz, [0], exchange="copy", periodic=True)
+    has = hasattr(job.lib, "stencil_slab_run_until")
+    k = job.info(0)["sweeps_per_round"]
+    out = {"round_info": job.round_info(), "steps": k,
+           "until_plan": {str(ev): job.until_plan(ev) for ev in EVERY} if has else None}
+
+    def fixed():
+        job.fill_initial("reference")
+        job.run(5 * k)  # the clock up, the shape's one-time choices
+        return job.run(a.sweeps)
+
+    def checked(every):
+        job.fill_initial("reference")
+        job.run(5 * k)
+        r = job.run_until(0.0, a.sweeps, check_every=every)
+        assert r.iterations == a.sweeps and not r.converged
+        return r.ms
+
+    fixed()
+    if has:
+        [checked(ev) for ev in EVERY]
+    fixed_ms, checked_ms = [], {ev: [] for ev in EVERY}
+    for _ in range(a.reps):
+        fixed_ms.append(fixed())
+        if has:
+            for ev in EVERY:
+                checked_ms[ev].append(checked(ev))
+    out["run_ms"] = [round(t, 3) for t in fixed_ms]
+    if has:
+        out["run_until_ms"] = {str(ev): [round(t, 3) for t in v] for ev, v in checked_ms.items()}
+    job.close()
+    if has and not a.lib:
+        # the face-signalled checking launch beside the plain face-signalled one: a slab with both halos
+        e = JacobiEngine(StencilSpec(dims=3, dtype=a.dtype, halo=k), nx, ny, nz, device=0, flags=_lib.HALO_LO | _lib.HALO_HI)
+        e.reset("random", 7)
+        stream = torch.cuda.current_stream()
+        word = torch.zeros(1, dtype=torch.int64, device=e.device)
+        sig = torch.zeros(4, dtype=torch.int32, device=e.device)
+        n32 = ctypes.c_int32(0)
+
+        def launches(check, count=20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(count):
+                if check:
+                    _lib.check(e.lib.stencil_sweepk_signal_update_max(
+                        ctypes.byref(e.layout), ctypes.c_void_p(e.a.data_ptr()), ctypes.c_void_p(e.b.data_ptr()), 0, nz, k,
+                        ctypes.c_void_p(sig.data_ptr()), None, ctypes.c_void_p(word.data_ptr()), ctypes.byref(n32),
+                        _stream_handle(stream)), "stencil_sweepk_signal_update_max", lib=e.lib)
+                else:
+                    e.sweepk_signal(e.a, e.b, 0, nz, k, sig, stream=stream)
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / count
+
+        launches(False, 2), launches(True, 2)
+        for _ in range(3):
+            launches(False)
+        plain, check = [], []
+        for _ in range(5):
+            plain.append(launches(False))
+            check.append(launches(True))
+        out["launch_ms"] = {"plain_signalled": [round(t, 4) for t in plain],
+                            "checking_signalled": [round(t, 4) for t in check]}
+    print(json.dumps(out))
+
+
+def slab_ab(a):
+    arms = [("fused", {"STENCIL_UNTIL_FUSED": "1"}, None), ("unfused", {"STENCIL_UNTIL_FUSED": "0"}, None),
+            ("fused_boundary_interior", {"STENCIL_UNTIL_FUSED": "1", "STENCIL_SLAB_SIGNAL": "0"}, None),
+            ("unfused_boundary_interior", {"STENCIL_UNTIL_FUSED": "0", "STENCIL_SLAB_SIGNAL": "0"}, None)]
+    if a.parent_lib:
+        arms.append(("parent", {}, a.parent_lib))
+    runs = {name: [] for name, _, _ in arms}
+    base = [sys.executable, os.path.abspath(__file__), "--slab-child", "--size", str(a.size), "--dtype", a.dtype,
+            "--reps", str(a.reps), "--sweeps", str(a.sweeps), "--nx", str(a.nx), "--ny", str(a.ny), "--nz", str(a.nz)]
+    for _ in range(a.rounds):
+        for name, env, lib in arms:
+            full = {k: v for k, v in os.environ.items() if k not in ("STENCIL_UNTIL_FUSED", "STENCIL_SLAB_SIGNAL")}
+            full.update(env)
+            p = subprocess.run(base + (["--lib", lib] if lib else []), capture_output=True, text=True, env=full)
+            if p.returncode != 0:
+                raise SystemExit(f"{name}: child failed\n{p.stdout}{p.stderr}")
+            runs[name].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    line = {"tool": "norm_bench --slab-ab", "grid": [a.nx or a.size, a.ny or a.size, a.nz or a.size], "dtype": a.dtype,
+            "sweeps": a.sweeps, "rounds": a.rounds, "job": "one slab, periodic, device copies", "arms": {}}
+    for name, rs in runs.items():
+        f = [t for r in rs for t in r["run_ms"]]
+        arm = {"round_info": rs[0]["round_info"], "steps": rs[0]["steps"], "until_plan": rs[0]["until_plan"],
+               "run_ms": {"median": statistics.median(f), "spread_percent": spread(f), "all": f}}
+        if "run_until_ms" in rs[0]:
+            arm["run_until_ms"] = {}
+            for ev in EVERY:
+                c = [t for r in rs for t in r["run_until_ms"][str(ev)]]
+                arm["run_until_ms"][str(ev)] = {
+                    "median": statistics.median(c), "spread_percent": spread(c), "all": c,
+                    "overhead_percent": round(100.0 * (statistics.median(c) / statistics.median(f) - 1.0), 2)}
+        if "launch_ms" in rs[0]:
+            pl = [t for r in rs for t in r["launch_ms"]["plain_signalled"]]
+            ck = [t for r in rs for t in r["launch_ms"]["checking_signalled"]]
+            arm["launch_ms"] = {"plain_signalled_median": statistics.median(pl), "plain_spread_percent": spread(pl),
+                                "checking_signalled_median": statistics.median(ck), "checking_spread_percent": spread(ck),
+                                "checking_vs_plain_percent":
+                                    round(100.0 * (statistics.median(ck) / statistics.median(pl) - 1.0), 2)}
+        line["arms"][name] = arm
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+
+
 def spread(v):
     return round(100.0 * (max(v) - min(v)) / statistics.median(v), 2)
 
@@ -166,7 +298,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="--fused-ab: children per arm")
     ap.add_argument("--parent-lib", default=None, help="--fused-ab: a third arm, another build of libstencil_hip.so")
     ap.add_argument("--launch-only", action="store_true", help="--fused-ab: only the launch timing")
+    ap.add_argument("--slab-ab", action="store_true", help="stencil_slab_run_until on a one-slab periodic job, in child processes")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--slab-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dtype", default="fp64", choices=["fp32", "fp64"])
     ap.add_argument("--reps", type=int, default=5)
@@ -176,6 +310,10 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a)
+    if a.slab_child:
+        return slab_child(a)
+    if a.slab_ab:
+        return slab_ab(a)
     if a.fused_ab:
         return fused_ab(a)
     torch.cuda.set_device(0)
