@@ -324,9 +324,12 @@ int signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, 
     tl_dry_launch = &info;
     int nsig = 0;
     void* fake_out = reinterpret_cast<void*>(uintptr_t(1));  // never touched in a dry launch
+    StripExtras x;
+    x.signal = true;
+    x.nsig = &nsig;
     const int rc = box27_supports(l.prob)
                        ? launch_boxk_signal(l, nullptr, fake_out, begin, end, steps, nullptr, nullptr, &nsig, nullptr)
-                       : launch_tkstrip_signal(l, nullptr, fake_out, begin, end, steps, nullptr, nullptr, &nsig, nullptr);
+                       : launch_tkstrip_default(l, nullptr, fake_out, begin, end, steps, x, nullptr);
     tl_dry_launch = nullptr;
     if (rc != STENCIL_OK) return rc;
     if (info.steps == 0) return set_error(STENCIL_EUNSUPPORTED, "no face-signalled launch was described");
@@ -552,43 +555,105 @@ int stencil_sweep2(const stencil_layout* l, const void* in, void* out, int64_t b
     return rc;
 }
 
+// What a stencil_sweepk* entry point was given beyond the sweep itself: the
+// launch's options (signal: face signalling; umax: the update maximum) and the
+// arguments that go with them.
+struct SweepkExtras {
+    bool signal = false, umax = false, gated = false;
+    uint32_t* counters = nullptr;
+    uint64_t* face_signal = nullptr;
+    uint64_t* update_max_bits = nullptr;
+    uint32_t gate_need = 0;
+    uint32_t* release_flag = nullptr;
+    int32_t* signals_per_face = nullptr;
+    SweepkExtras& signalling(uint32_t* c, uint64_t* fsig, int32_t* per_face) {
+        return signal = true, counters = c, face_signal = fsig, signals_per_face = per_face, *this;
+    }
+    SweepkExtras& checking(uint64_t* bits) { return umax = true, update_max_bits = bits, *this; }
+    SweepkExtras& gate(uint32_t need, uint32_t* flag) { return gated = true, gate_need = need, release_flag = flag, *this; }
+};
+
+// The argument checks of the six entry points, in the order in which they
+// fire (where two could, the earlier one wins: part of each entry point's
+// behaviour).
+static int sweepk_args(const stencil_layout* l, const void* in, const void* out, int64_t begin, int64_t end,
+                       int32_t steps, const SweepkExtras& e) {
+    if (int rc = check_layout(l)) return rc;
+    if (e.umax) {
+        if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 3..5 (got %d)", steps);
+        if (!temporal2_supports(l->prob))
+            return set_error(STENCIL_EUNSUPPORTED, "%supdate-max sweeps cover the 3D r=1 naive 7-point star only",
+                             e.signal ? "face-signalled " : "");
+    } else if (!e.signal) {
+        if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 1..5 (got %d)", steps);
+        // the box's K = 5 strip shapes are debug configurations only (DESIGN.md
+        // §9.2e: they lose to K = 4); the product library has no K = 5 box launch
+        const int box_max = stencil_debug_knobs() ? 5 : 4;
+        if (!temporal2_supports(l->prob) && !(box27_supports(l->prob) && steps <= box_max))
+            return set_error(STENCIL_EUNSUPPORTED,
+                             "3- to 5-step fused sweeps cover the 3D r=1 naive 7-point star (3..5) and box (3..%d) only",
+                             box_max);
+    }  // (a face-signalled launch that does not check takes its steps and stencil errors from the launch)
+    if (e.signal && !e.counters) return set_error(STENCIL_EINVAL, "null counters");
+    if (e.umax && !e.update_max_bits) return set_error(STENCIL_EINVAL, "null update_max_bits");
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
+    // a face-signalled range shorter than `steps` planes would signal one face
+    // only: the checking launches refuse it
+    if (e.signal && e.umax && end - begin < steps)
+        return set_error(STENCIL_EINVAL, "a face-signalled range needs at least %d planes (got %lld)", steps,
+                         (long long)(end - begin));
+    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
+    return STENCIL_OK;
+}
+
+// The entry points' common tail: a launch that succeeded reports its adds per
+// face (face-signalled launches) and clears the thread's error.
+static int sweepk_done(int rc, int nsig, int32_t* signals_per_face) {
+    if (rc == STENCIL_OK) {
+        if (signals_per_face) *signals_per_face = nsig;
+        clear_error();
+    }
+    return rc;
+}
+
 int stencil_sweepk(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end, int32_t steps,
                    void* stream) {
     if (steps == 1) return stencil_sweep(l, in, out, begin, end, stream);
     if (steps == 2) return stencil_sweep2(l, in, out, begin, end, stream);
-    if (int rc = check_layout(l)) return rc;
-    if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 1..5 (got %d)", steps);
+    if (int rc = sweepk_args(l, in, out, begin, end, steps, SweepkExtras{})) return rc;
+    const int rc = box27_supports(l->prob) ? launch_boxk(*l, in, out, begin, end, steps, as_stream(stream))
+                                           : launch_temporalk(*l, in, out, begin, end, steps, as_stream(stream));
+    return sweepk_done(rc, 0, nullptr);
+}
+
+// The entry points with extras: the default strip launch.  A face-signalled
+// launch of the box goes to the box kernel's, which has no halo gate.
+static int sweepk_extras(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end, int32_t steps,
+                         const SweepkExtras& e, void* stream) {
+    if (int rc = sweepk_args(l, in, out, begin, end, steps, e)) return rc;
     const bool box = box27_supports(l->prob);
-    // the box's K = 5 strip shapes are debug configurations only (DESIGN.md
-    // §9.2e: they lose to K = 4); the product library has no K = 5 box launch
-    const int box_max = stencil_debug_knobs() ? 5 : 4;
-    if (!temporal2_supports(l->prob) && !(box && steps <= box_max))
-        return set_error(STENCIL_EUNSUPPORTED,
-                         "3- to 5-step fused sweeps cover the 3D r=1 naive 7-point star (3..5) and box (3..%d) only",
-                         box_max);
-    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
-        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
-    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
-    const int rc = box ? launch_boxk(*l, in, out, begin, end, steps, as_stream(stream))
-                       : launch_temporalk(*l, in, out, begin, end, steps, as_stream(stream));
-    if (rc == STENCIL_OK) clear_error();
-    return rc;
+    if (e.gated && box) return set_error(STENCIL_EUNSUPPORTED, "the halo-gated launch is the 7-point star's");
+    int nsig = 0;
+    StripExtras x;
+    x.signal = e.signal;
+    x.sig = e.counters;
+    x.fsig = reinterpret_cast<unsigned long long*>(e.face_signal);
+    x.umax = reinterpret_cast<unsigned long long*>(e.update_max_bits);
+    x.nsig = &nsig;
+    if (e.gated) {
+        x.gate.word = e.counters + 3;
+        x.gate.release = e.release_flag;
+        x.gate.need = e.gate_need;
+    }
+    const int rc = box ? launch_boxk_signal(*l, in, out, begin, end, steps, x.sig, x.fsig, &nsig, as_stream(stream))
+                       : launch_tkstrip_default(*l, in, out, begin, end, steps, x, as_stream(stream));
+    return sweepk_done(rc, nsig, e.signals_per_face);
 }
 
 int stencil_sweepk_update_max(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
                               int32_t steps, uint64_t* update_max_bits, void* stream) {
-    if (int rc = check_layout(l)) return rc;
-    if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 3..5 (got %d)", steps);
-    if (!temporal2_supports(l->prob))
-        return set_error(STENCIL_EUNSUPPORTED, "update-max sweeps cover the 3D r=1 naive 7-point star only");
-    if (!update_max_bits) return set_error(STENCIL_EINVAL, "null update_max_bits");
-    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
-        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
-    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
-    const int rc = launch_tkstrip_update_max(*l, in, out, begin, end, steps,
-                                             reinterpret_cast<unsigned long long*>(update_max_bits), as_stream(stream));
-    if (rc == STENCIL_OK) clear_error();
-    return rc;
+    return sweepk_extras(l, in, out, begin, end, steps, SweepkExtras{}.checking(update_max_bits), stream);
 }
 
 int stencil_sweepk_geometry(const stencil_layout* l, int64_t begin, int64_t end, int32_t steps, int64_t* workgroups,
@@ -614,108 +679,39 @@ int stencil_sweepk_geometry(const stencil_layout* l, int64_t begin, int64_t end,
     return STENCIL_OK;
 }
 
-
 int stencil_sweepk_signal(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
                           int32_t steps, uint32_t* counters, uint64_t* face_signal, int32_t* signals_per_face,
                           void* stream) {
-    if (int rc = check_layout(l)) return rc;
-    if (!counters) return set_error(STENCIL_EINVAL, "null counters");
-    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
-        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
-    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
-    int nsig = 0;
-    auto* fsig = reinterpret_cast<unsigned long long*>(face_signal);
-    const int rc = box27_supports(l->prob)
-                       ? launch_boxk_signal(*l, in, out, begin, end, steps, counters, fsig, &nsig, as_stream(stream))
-                       : launch_tkstrip_signal(*l, in, out, begin, end, steps, counters, fsig, &nsig,
-                                               as_stream(stream));
-    if (rc == STENCIL_OK) {
-        if (signals_per_face) *signals_per_face = nsig;
-        clear_error();
-    }
-    return rc;
+    return sweepk_extras(l, in, out, begin, end, steps,
+                         SweepkExtras{}.signalling(counters, face_signal, signals_per_face), stream);
 }
 
 int stencil_sweepk_signal_gated(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
                                 int32_t steps, uint32_t* counters, uint64_t* face_signal, uint32_t gate_need,
                                 uint32_t* release_flag, int32_t* signals_per_face, void* stream) {
-    if (int rc = check_layout(l)) return rc;
-    if (!counters) return set_error(STENCIL_EINVAL, "null counters");
-    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
-        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
-    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
-    if (box27_supports(l->prob)) return set_error(STENCIL_EUNSUPPORTED, "the halo-gated launch is the 7-point star's");
-    int nsig = 0;
-    StripGate gate;
-    gate.word = counters + 3;
-    gate.release = release_flag;
-    gate.need = gate_need;
-    const int rc = launch_tkstrip_signal(*l, in, out, begin, end, steps, counters,
-                                         reinterpret_cast<unsigned long long*>(face_signal), &nsig,
-                                         as_stream(stream), gate);
-    if (rc == STENCIL_OK) {
-        if (signals_per_face) *signals_per_face = nsig;
-        clear_error();
-    }
-    return rc;
-}
-
-// The face-signalled launches that also report their update: the checks the
-// plain checking launch makes, then stencil_sweepk_signal's.  A range shorter
-// than `steps` planes would signal one face only: refused here.
-static int signal_update_max_args(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
-                                  int32_t steps, const uint32_t* counters, const uint64_t* update_max_bits) {
-    if (int rc = check_layout(l)) return rc;
-    if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "steps must be 3..5 (got %d)", steps);
-    if (!temporal2_supports(l->prob))
-        return set_error(STENCIL_EUNSUPPORTED,
-                         "face-signalled update-max sweeps cover the 3D r=1 naive 7-point star only");
-    if (!counters) return set_error(STENCIL_EINVAL, "null counters");
-    if (!update_max_bits) return set_error(STENCIL_EINVAL, "null update_max_bits");
-    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
-        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
-    if (end - begin < steps)
-        return set_error(STENCIL_EINVAL, "a face-signalled range needs at least %d planes (got %lld)", steps,
-                         (long long)(end - begin));
-    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
-    return STENCIL_OK;
+    return sweepk_extras(l, in, out, begin, end, steps,
+                         SweepkExtras{}.signalling(counters, face_signal, signals_per_face).gate(gate_need, release_flag),
+                         stream);
 }
 
 int stencil_sweepk_signal_update_max(const stencil_layout* l, const void* in, void* out, int64_t begin, int64_t end,
                                      int32_t steps, uint32_t* counters, uint64_t* face_signal,
                                      uint64_t* update_max_bits, int32_t* signals_per_face, void* stream) {
-    if (int rc = signal_update_max_args(l, in, out, begin, end, steps, counters, update_max_bits)) return rc;
-    int nsig = 0;
-    const int rc = launch_tkstrip_signal_update_max(*l, in, out, begin, end, steps, counters,
-                                                    reinterpret_cast<unsigned long long*>(face_signal),
-                                                    reinterpret_cast<unsigned long long*>(update_max_bits), &nsig,
-                                                    as_stream(stream));
-    if (rc == STENCIL_OK) {
-        if (signals_per_face) *signals_per_face = nsig;
-        clear_error();
-    }
-    return rc;
+    return sweepk_extras(l, in, out, begin, end, steps,
+                         SweepkExtras{}.signalling(counters, face_signal, signals_per_face).checking(update_max_bits),
+                         stream);
 }
 
 int stencil_sweepk_signal_update_max_gated(const stencil_layout* l, const void* in, void* out, int64_t begin,
                                            int64_t end, int32_t steps, uint32_t* counters, uint64_t* face_signal,
                                            uint64_t* update_max_bits, uint32_t gate_need, uint32_t* release_flag,
                                            int32_t* signals_per_face, void* stream) {
-    if (int rc = signal_update_max_args(l, in, out, begin, end, steps, counters, update_max_bits)) return rc;
-    int nsig = 0;
-    StripGate gate;
-    gate.word = counters + 3;
-    gate.release = release_flag;
-    gate.need = gate_need;
-    const int rc = launch_tkstrip_signal_update_max(*l, in, out, begin, end, steps, counters,
-                                                    reinterpret_cast<unsigned long long*>(face_signal),
-                                                    reinterpret_cast<unsigned long long*>(update_max_bits), &nsig,
-                                                    as_stream(stream), gate);
-    if (rc == STENCIL_OK) {
-        if (signals_per_face) *signals_per_face = nsig;
-        clear_error();
-    }
-    return rc;
+    return sweepk_extras(l, in, out, begin, end, steps,
+                         SweepkExtras{}
+                             .signalling(counters, face_signal, signals_per_face)
+                             .checking(update_max_bits)
+                             .gate(gate_need, release_flag),
+                         stream);
 }
 
 int stencil_exchange_done(uint32_t* counters, uint32_t value, void* stream) {
@@ -1260,9 +1256,9 @@ int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t ma
             }
             if (!word.dev) STENCIL_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&word.dev), sizeof(uint64_t), s));
             STENCIL_HIP_CHECK(hipMemsetAsync(word.dev, 0, sizeof(uint64_t), s));
-            if (int rc = launch_tkstrip_update_max(*l, cur, old, 0, n, int(k),
-                                                   reinterpret_cast<unsigned long long*>(word.dev), s))
-                return rc;
+            StripExtras x;
+            x.umax = reinterpret_cast<unsigned long long*>(word.dev);
+            if (int rc = launch_tkstrip_default(*l, cur, old, 0, n, int(k), x, s)) return rc;
             std::swap(cur, old);
             done += block;
             uint64_t bits = 0;

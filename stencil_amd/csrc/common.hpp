@@ -201,24 +201,27 @@ struct StripGate {
     const uint32_t* word = nullptr;
     uint32_t* release = nullptr;
     uint32_t need = 0;
-    // a face-signalled launch that also reports its update
-    // (stencil_sweepk_signal_update_max): the word, which plain checking
-    // launches pass in the kernel's fsig argument
+    // a face-signalled launch that also reports its update: the word, as the
+    // kernel takes it (set by the launch from StripExtras::umax, never by callers)
     unsigned long long* umax = nullptr;
 };
-int launch_tkstrip_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
-                          unsigned* sig, unsigned long long* fsig, int* nsig, hipStream_t s,
-                          const StripGate& gate = StripGate{});
-// The default strip shapes as plain launches that also raise *word (8 bytes of
-// device memory, a double's bit pattern) to max |u^K - u^(K-1)| over the cells
-// they store (stencil_sweepk_update_max)
-int launch_tkstrip_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
-                              unsigned long long* word, hipStream_t s);
-// launch_tkstrip_signal's launches that also raise *word as launch_tkstrip_update_max does
-// (stencil_sweepk_signal_update_max)
-int launch_tkstrip_signal_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
-                                     int steps, unsigned* sig, unsigned long long* fsig, unsigned long long* word,
-                                     int* nsig, hipStream_t s, const StripGate& gate = StripGate{});
+// What a default-shape strip launch takes beyond the sweep itself, and with it
+// the launch's two independent options: face signalling (`signal`;
+// stencil_sweepk_signal) and the update maximum (`umax` non-null;
+// stencil_sweepk_update_max).
+struct StripExtras {
+    bool signal = false;
+    unsigned* sig = nullptr;             // signal: the two face counters
+    unsigned long long* fsig = nullptr;  // signal: the face-signal word (HIP signal memory), or null
+    // 8 bytes of device memory, a double's bit pattern: raised to max |u^K - u^(K-1)| over the cells the
+    // launch stores
+    unsigned long long* umax = nullptr;
+    StripGate gate;                      // signal: the halo gate (a null word: none)
+    int* nsig = nullptr;                 // signal, out: the adds per face (one per tile)
+};
+// The default strip shapes with at least one of the extras' options
+int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
+                           const StripExtras& x, hipStream_t s);
 // stencil_iterate_until's rule (api.hip): the sweeps of the checking K-step launch that ends a block of
 // `block` sweeps on problem `p`, or 0 when the block keeps the un-fused check
 int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm);

@@ -884,12 +884,64 @@ __global__ void __launch_bounds__(64 * NW)
 
 int senv_int(const char* name, int dflt) { return knob(name, dflt); }
 
-template <typename T, int V, int RY, int NW, int K, bool DB = true, int DIAG = 0, bool SIG = false, int NS = 4,
-          bool FP = true, bool HL = false, bool SPLIT = false, bool UMAX = false>
+// A strip shape on the host: the five numbers every shape states -- element
+// type, cells per lane, rows per strip, waves, fused sweeps -- and the kernel's
+// options by name (the comment above the kernel describes each), so a shape
+// says only what differs from the default: two boundary-row buffers, no face
+// signalling, the interior fast path compiled in, histories in registers, one
+// strip per wave, no update maximum, NS = 4, DIAG = 0.
+enum : unsigned {
+    kOneBuf = 1,    // one boundary-row buffer, a second barrier per step (DB = false)
+    kSig = 2,       // SIG: face signalling
+    kNoFast = 4,    // no per-step interior fast path (FP = false)
+    kHistLds = 8,   // HL: stage 1's history in LDS
+    kSplit = 16,    // SPLIT: two strips per wave
+    kUmax = 32,     // UMAX: the launch reports its update maximum
+};
+template <typename T_, int V_, int RY_, int NW_, int K_, unsigned OPT = 0, int NS_ = 4, int DIAG_ = 0>
+struct Shape {
+    using T = T_;
+    static constexpr int V = V_, RY = RY_, NW = NW_, K = K_, NS = NS_, DIAG = DIAG_;
+    static constexpr bool DB = !(OPT & kOneBuf), SIG = OPT & kSig, FP = !(OPT & kNoFast), HL = OPT & kHistLds,
+                          SPLIT = OPT & kSplit, UMAX = OPT & kUmax;
+    using Tile = StripTile<T, V, RY, NW, K, DB, SPLIT>;
+};
+// The one place that maps a shape onto the kernel's positional parameters.
+template <class S, bool TIER = false>
+auto strip_kernel() {
+    return tkstrip_7pt<typename S::T, S::V, S::RY, S::NW, S::K, S::DB, S::DIAG, S::SIG, S::NS, S::FP, S::HL, TIER,
+                       S::SPLIT, S::UMAX>;
+}
+
+// The default shapes (8 waves each): cells per lane and rows per strip by
+// [fp64][K - 3].
+constexpr struct {
+    int v, ry;
+} kDefaultStrip[2][3] = {{{4, 4}, {2, 7}, {2, 5}},   // fp32 K = 3, 4, 5
+                         {{2, 4}, {1, 7}, {1, 5}}};  // fp64 K = 3, 4, 5
+// Rows per strip of the default shape of (T, K) under the launch's options
+// {kSig, kUmax}.  Two launches run 6-row strips at K = 4, bitwise the same
+// sweep (120 x 40 / 64 x 40 tiles); DESIGN.md §5.6 has the resource table.
+template <typename T, int K, unsigned OPT>
+constexpr int default_rows() {
+    // fp32 checking launches, signalled or not: the default 7-row shape (253 VGPRs) spills a VGPR once it
+    // holds the accumulator (8 B of scratch per lane); 6 rows take 223 and none
+    if (sizeof(T) == 4 && K == 4 && (OPT & kUmax)) return 6;
+    // fp64 signalled checking launches: the plain signalled 7-row shape already spills (52 B of scratch per
+    // lane), with the accumulator 80 B; 6 rows take none
+    if (sizeof(T) == 8 && K == 4 && (OPT & kSig) && (OPT & kUmax)) return 6;
+    return kDefaultStrip[sizeof(T) == 8][K - 3].ry;
+}
+template <typename T, int K, unsigned OPT = 0, int NS = 4>
+using DefaultShape = Shape<T, kDefaultStrip[sizeof(T) == 8][K - 3].v, default_rows<T, K, OPT>(), 8, K, OPT, NS>;
+
+template <class S>
 int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, hipStream_t s,
-              unsigned* sig = nullptr, int* nsig = nullptr, unsigned long long* fsig = nullptr,
-              const StripGate& gate = StripGate{}) {
-    using Tl = StripTile<T, V, RY, NW, K, DB, SPLIT>;
+              const StripExtras& x = StripExtras{}) {
+    using T = typename S::T;
+    using Tl = typename S::Tile;
+    constexpr int V = S::V, RY = S::RY, NW = S::NW, K = S::K;
+    constexpr bool SIG = S::SIG, HL = S::HL;
     static_assert(Tl::lds_bytes + (HL ? size_t(2) * Tl::RH * Tl::RW * sizeof(T) : 0) <= 160 * 1024, "LDS budget");
     const Geom g = geom_of(l);
     const int64_t nz = end - begin;
@@ -897,7 +949,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     if ((g.plane + g.row + 64) * int64_t(sizeof(T)) >= (int64_t(1) << 32) || g.nz + 2 * K >= (int64_t(1) << 30))
         return set_error(STENCIL_EINVAL, "plane too large for tkstrip (4 GiB per plane, 2^30 planes)");
     const int64_t gx = (g.nx + Tl::TX - 1) / Tl::TX, gy = (g.ny + Tl::TY - 1) / Tl::TY;
-    auto kern = tkstrip_7pt<T, V, RY, NW, K, DB, DIAG, SIG, NS, FP, HL, false, SPLIT, UMAX>;
+    auto kern = strip_kernel<S>();
     const int64_t tiles = gx * gy;
     int dev = 0, slots = 0;
     STENCIL_HIP_CHECK(hipGetDevice(&dev));
@@ -963,7 +1015,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
         while (nch > 1 && ((nz + nch - 1) / nch < K || last(nch) < K)) --nch;
         zc = int((nz + nch - 1) / nch);
         nb = tiles * nch;
-        if (nsig) *nsig = int(tiles);
+        if (x.nsig) *x.nsig = int(tiles);
     }
     const int* sched = nullptr;
     std::atomic<int>* verdict = nullptr;
@@ -1033,12 +1085,18 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     const bool whole = !halo && begin == 0 && end == g.nz;
     const int xcd_dflt = tiles > 2 * int64_t(slots) ? (sizeof(T) == 4 ? 16 : (whole ? 8 : 0)) : 0;
     const int xcd_pw = !SIG && zc > 0 ? senv_int("STENCIL_TK_XCD", xcd_dflt) : 0;
+    // The run-time extras as the kernel takes them.  A face-signalled launch needs the kernel's fsig
+    // argument for its face-signal word, so the update word travels in fsig on plain launches and in
+    // gate.umax on signalled ones (UMAX / SIG + UMAX above the kernel).
+    StripGate gate = SIG ? x.gate : StripGate{};
+    unsigned long long* fsig = SIG ? x.fsig : nullptr;
+    if (S::UMAX) (SIG ? gate.umax : fsig) = x.umax;
     auto launch = [&](bool packed) {
         const int64_t n = packed ? nb : (xcd_pw > 0 ? (nb_equal + 7) / 8 * 8 : nb_equal);
         hipLaunchKernelGGL(kern, dim3(unsigned(n)), dim3(64, NW, 1), 0, s,
                            static_cast<const T*>(in), static_cast<T*>(out), g, int(begin), int(end), zc, int(gx),
-                           int(gy), int(lo), int(hi), avg_weight<T>(l.prob), sig, fsig, packed ? sched : nullptr,
-                           fast_of(packed), packed ? 0 : xcd_pw, TierArgs{}, SIG ? gate : StripGate{});
+                           int(gy), int(lo), int(hi), avg_weight<T>(l.prob), SIG ? x.sig : nullptr, fsig,
+                           packed ? sched : nullptr, fast_of(packed), packed ? 0 : xcd_pw, TierArgs{}, gate);
         return hipGetLastError();
     };
     if (sched && verdict && verdict->load() == kPackUntested) return pick_schedule(verdict, s, launch);
@@ -1049,7 +1107,8 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
 
 // ---- the two-tier launch (TIER, above): host side --------------------------
 #ifndef STRIP_ILP_TU
-using TierKernelShape = StripTile<double, 1, 7, 8, 4, true>;
+using TierShape = Shape<double, 1, 7, 8, 4, kNoFast | kHistLds>;  // launched with TIER
+using TierKernelShape = TierShape::Tile;
 constexpr int kTierSlots = 16;  // R: plane slots of the producer -> consumer ring (2.2 MB each at 512^2 fp64)
 
 int tier_tiles(const stencil_layout& l, int64_t* tiles) {
@@ -1072,9 +1131,7 @@ bool tier_eligible(const stencil_layout& l) {
     int64_t tiles = 0;
     tier_tiles(l, &tiles);
     int slots = 0;
-    if (resident_slots(tkstrip_7pt<double, 1, 7, 8, 4, true, 0, false, 4, false, true, true>, 64 * 8, &slots) !=
-        STENCIL_OK)
-        return false;
+    if (resident_slots(strip_kernel<TierShape, true>(), 64 * 8, &slots) != STENCIL_OK) return false;
     return 2 * tiles <= slots;
 }
 
@@ -1149,7 +1206,7 @@ int tier_launch(const stencil_layout& l, const void* in, void* out, TierJob* j, 
     const int64_t gy = (g.ny + TierKernelShape::TY - 1) / TierKernelShape::TY;
     if ((g.plane + g.row + 64) * int64_t(sizeof(double)) >= (int64_t(1) << 32) || g.nz >= (int64_t(1) << 30))
         return set_error(STENCIL_EINVAL, "plane too large for the two-tier launch");
-    auto kern = tkstrip_7pt<double, 1, 7, 8, 4, true, 0, false, 4, false, true, true>;
+    auto kern = strip_kernel<TierShape, true>();
     const int fast = 1;  // few tiles: the interior fast path pays (as the packed regime)
     hipLaunchKernelGGL(kern, dim3(unsigned(2 * j->tiles)), dim3(64, 8, 1), 0, s, static_cast<const double*>(in),
                        static_cast<double*>(out), g, 0, int(g.nz), 0, int(gx), int(gy), 0, 0,
@@ -1192,15 +1249,15 @@ int STRIP_ILP_FN(const stencil_layout& l, const void* in, void* out, int64_t beg
                  hipStream_t s) {
 #ifdef TK_PROBE_SPLIT64
     if (l.prob.dtype == STENCIL_F64 && steps == 4)
-        return launch_st<double, 2, TK_PROBE_SPLIT64, 8, 4, false, 0, false, 4, true, true, true>(l, in, out, begin, end, s);
+        return launch_st<Shape<double, 2, TK_PROBE_SPLIT64, 8, 4, kOneBuf | kHistLds | kSplit>>(l, in, out, begin, end, s);
 #endif
-    if (l.prob.dtype == STENCIL_F64 && steps == 4) return launch_st<double, 1, 7, 8, 4>(l, in, out, begin, end, s);
+    if (l.prob.dtype == STENCIL_F64 && steps == 4) return launch_st<DefaultShape<double, 4>>(l, in, out, begin, end, s);
 #ifdef TK_PROBE_SPLIT
     if (l.prob.dtype == STENCIL_F32 && steps == 5)
-        return launch_st<float, 4, TK_PROBE_SPLIT, 8, 5, false, 0, false, 4, true, true, true>(l, in, out, begin, end, s);
+        return launch_st<Shape<float, 4, TK_PROBE_SPLIT, 8, 5, kOneBuf | kHistLds | kSplit>>(l, in, out, begin, end, s);
 #endif
     if (l.prob.dtype == STENCIL_F32 && steps == 5)
-        return launch_st<float, 2, 5, 8, 5, true, 0, false, TK_ILP_NS32>(l, in, out, begin, end, s);
+        return launch_st<DefaultShape<float, 5, 0, TK_ILP_NS32>>(l, in, out, begin, end, s);
     return set_error(STENCIL_EINVAL, "no max-ILP strip shape for %d steps", steps);
 }
 #else
@@ -1514,214 +1571,153 @@ int pick_schedule(std::atomic<int>* verdict, hipStream_t s, const std::function<
 
 // Whether launch_st would consider the packed schedule for this shape (a
 // single grid of at most 2 tiles per CU slot: packed_schedule's own test).
-template <typename T, int V, int RY, int NW, int K>
+template <class S>
 static bool packed_regime(const stencil_layout& l) {
-    using Tl = StripTile<T, V, RY, NW, K, true>;
+    using Tl = typename S::Tile;
     if (l.prob.flags & (STENCIL_HALO_LO | STENCIL_HALO_HI)) return false;
     const Geom g = geom_of(l);
     const int64_t tiles = ((g.nx + Tl::TX - 1) / Tl::TX) * ((g.ny + Tl::TY - 1) / Tl::TY);
     int slots = 0;
-    if (resident_slots(tkstrip_7pt<T, V, RY, NW, K, true>, 64 * NW, &slots) != STENCIL_OK) return false;
+    if (resident_slots(strip_kernel<S>(), 64 * S::NW, &slots) != STENCIL_OK) return false;
     return tiles <= 2 * int64_t(slots);
 }
 
-// cfg = RY*100 + NW (rows per wave x waves); 0 = default shape.
+// The default shape of (dtype, steps) under the launch's options {kSig, kUmax}: every default launch --
+// plain, face-signalled, checking, both -- takes its shape from kDefaultStrip / default_rows here.
+template <unsigned OPT>
+static int launch_default(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
+                          hipStream_t s, const StripExtras& x, const char* what) {
+    const bool f32 = l.prob.dtype == STENCIL_F32;
+    switch (steps) {
+    case 3:
+        return f32 ? launch_st<DefaultShape<float, 3, OPT>>(l, in, out, begin, end, s, x)
+                   : launch_st<DefaultShape<double, 3, OPT>>(l, in, out, begin, end, s, x);
+    case 4:
+        return f32 ? launch_st<DefaultShape<float, 4, OPT>>(l, in, out, begin, end, s, x)
+                   : launch_st<DefaultShape<double, 4, OPT>>(l, in, out, begin, end, s, x);
+    case 5:
+        return f32 ? launch_st<DefaultShape<float, 5, OPT>>(l, in, out, begin, end, s, x)
+                   : launch_st<DefaultShape<double, 5, OPT>>(l, in, out, begin, end, s, x);
+    default: return set_error(STENCIL_EINVAL, "%s: steps must be 3, 4 or 5 (got %d)", what, steps);
+    }
+}
+
+// cfg = RY*100 + NW (rows per wave x waves); 0 (or a code without a row) = default shape.
 int launch_tkstrip(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                    int cfg, hipStream_t s) {
     if (!temporal2_supports(l.prob))
         return set_error(STENCIL_EUNSUPPORTED, "tkstrip supports the 3D r=1 naive 7-point star only");
     // debug cfg 97: the max-ILP shapes from kernels_strip_probe.hip (debug library only)
     if (cfg == 97) return launch_tkstrip_probe(l, in, out, begin, end, steps, s);
-    if (l.prob.dtype == STENCIL_F32) {
-        if (steps == 3) {
-            switch (cfg) {
-            case 416: return launch_st<float, 4, 4, 16, 3, false>(l, in, out, begin, end, s);
-            case 808: return launch_st<float, 4, 8, 8, 3>(l, in, out, begin, end, s);
-            case 20808: return launch_st<float, 2, 8, 8, 3>(l, in, out, begin, end, s);
-            case 20608: return launch_st<float, 2, 6, 8, 3>(l, in, out, begin, end, s);
-            default: return launch_st<float, 4, 4, 8, 3>(l, in, out, begin, end, s);
-            }
-        }
-        if (steps == 4) {
-            switch (cfg) {
-            case 20808: return launch_st<float, 2, 8, 8, 4>(l, in, out, begin, end, s);
-            case 404: return launch_st<float, 4, 4, 8, 4>(l, in, out, begin, end, s);
-            default: return launch_st<float, 2, 7, 8, 4>(l, in, out, begin, end, s);
-            }
-        }
-    } else {
-        if (steps == 3) {
-            switch (cfg) {
-            case 416: return launch_st<double, 2, 4, 16, 3, false>(l, in, out, begin, end, s);
-            case 10408: return launch_st<double, 2, 4, 8, 3, false>(l, in, out, begin, end, s);
-            case 608: return launch_st<double, 2, 6, 8, 3>(l, in, out, begin, end, s);
-            case 216: return launch_st<double, 2, 2, 16, 3, false>(l, in, out, begin, end, s);
-            case 10808: return launch_st<double, 1, 8, 8, 3>(l, in, out, begin, end, s);
-            case 10608: return launch_st<double, 1, 6, 8, 3>(l, in, out, begin, end, s);
-#ifdef STENCIL_DIAG
-            // timing experiments only, results wrong on purpose: never in the product build
-            case 91: return launch_st<double, 2, 4, 8, 3, true, 1>(l, in, out, begin, end, s);
-            case 92: return launch_st<double, 2, 4, 8, 3, true, 2>(l, in, out, begin, end, s);
-            case 93: return launch_st<double, 2, 4, 8, 3, true, 3>(l, in, out, begin, end, s);
-#endif
-            default: return launch_st<double, 2, 4, 8, 3>(l, in, out, begin, end, s);
-            }
-        }
-        if (steps == 4) {
-            switch (cfg) {
-            case 10808: return launch_st<double, 1, 8, 8, 4>(l, in, out, begin, end, s);
-            // the default shape from this file's build whatever the grid (AUTO takes the max-ILP build on
-            // packed-regime grids)
-            case 10708: return launch_st<double, 1, 7, 8, 4>(l, in, out, begin, end, s);
-            case 10608: return launch_st<double, 1, 6, 8, 4>(l, in, out, begin, end, s);
-            case 404: return launch_st<double, 2, 4, 8, 4>(l, in, out, begin, end, s);
-            case 510708: return launch_st<double, 1, 7, 8, 4, true, 0, false, 5>(l, in, out, begin, end, s);
-            // the default shape without the interior fast path (no duplicated step)
-            case 710708: return launch_st<double, 1, 7, 8, 4, true, 0, false, 4, false>(l, in, out, begin, end, s);
-            case 510608: return launch_st<double, 1, 6, 8, 4, true, 0, false, 5>(l, in, out, begin, end, s);
-            case 610608: return launch_st<double, 1, 6, 8, 4, true, 0, false, 6>(l, in, out, begin, end, s);
-            case 610508: return launch_st<double, 1, 5, 8, 4, true, 0, false, 6>(l, in, out, begin, end, s);
-            // stage 1's history in LDS (HL): 8-row strips at K = 4
-            case 810808: return launch_st<double, 1, 8, 8, 4, true, 0, false, 4, true, true>(l, in, out, begin, end, s);
-            case 810708: return launch_st<double, 1, 7, 8, 4, true, 0, false, 4, true, true>(l, in, out, begin, end, s);
-            // SPLIT (two strips per wave, 32 lanes x 2 cells: 16-B lane loads): 64 x 64 / 64 x 48 regions
-            case 1020408: return launch_st<double, 2, 4, 8, 4, true, 0, false, 4, true, false, true>(l, in, out, begin, end, s);
-            case 1020308: return launch_st<double, 2, 3, 8, 4, true, 0, false, 4, true, false, true>(l, in, out, begin, end, s);
-            case 1820408: return launch_st<double, 2, 4, 8, 4, false, 0, false, 4, true, true, true>(l, in, out, begin, end, s);
-            // 9-row strips without the fast path: 72 rows for 64 output rows (512 = 8 x 64)
-            case 820908: return launch_st<double, 1, 9, 8, 4, true, 0, false, 4, false, true>(l, in, out, begin, end, s);
-            default:
-                // grids of at most 2 tiles per CU slot (packed schedule, fast path): the max-ILP build
-                if (packed_regime<double, 1, 7, 8, 4>(l)) return launch_tkstrip_ilp(l, in, out, begin, end, 4, s);
-                return launch_st<double, 1, 7, 8, 4>(l, in, out, begin, end, s);
-            }
-        }
-    }
-    if (steps == 5) {
-        if (l.prob.dtype == STENCIL_F32) {
-            switch (cfg) {
-            case 20608: return launch_st<float, 2, 6, 8, 5>(l, in, out, begin, end, s);
-            // stage 1's history in LDS (HL): 6-row strips (226 VGPRs); 7 rows with one boundary buffer (254)
-            case 820608: return launch_st<float, 2, 6, 8, 5, true, 0, false, 4, true, true>(l, in, out, begin, end, s);
-            case 830708: return launch_st<float, 2, 7, 8, 5, false, 0, false, 4, true, true>(l, in, out, begin, end, s);
-            // the default shape from this file's build (AUTO takes the max-ILP build)
-            case 20508: return launch_st<float, 2, 5, 8, 5>(l, in, out, begin, end, s);
-            // input planes loaded 3 / 4 planes ahead (NS = 5 / 6) instead of 2
-            case 520508: return launch_st<float, 2, 5, 8, 5, true, 0, false, 5>(l, in, out, begin, end, s);
-            case 620508: return launch_st<float, 2, 5, 8, 5, true, 0, false, 6>(l, in, out, begin, end, s);
-            // 4 cells per lane (256-wide regions: 16-B lane loads), one boundary-row buffer (80 KB of LDS)
-            case 40408: return launch_st<float, 4, 4, 8, 5, false>(l, in, out, begin, end, s);
-            case 840408: return launch_st<float, 4, 4, 8, 5, false, 0, false, 4, true, true>(l, in, out, begin, end, s);
-            // SPLIT (two strips per wave, 32 lanes x 4 cells: 16-B lane loads): 128 x 32 / 128 x 48 regions
-            case 1040208: return launch_st<float, 4, 2, 8, 5, true, 0, false, 4, true, false, true>(l, in, out, begin, end, s);
-            case 1040308: return launch_st<float, 4, 3, 8, 5, true, 0, false, 4, true, false, true>(l, in, out, begin, end, s);
-            case 1030308: return launch_st<float, 4, 3, 8, 5, false, 0, false, 4, true, false, true>(l, in, out, begin, end, s);
-            case 1030212: return launch_st<float, 4, 2, 12, 5, false, 0, false, 4, true, false, true>(l, in, out, begin, end, s);
-            case 1830308: return launch_st<float, 4, 3, 8, 5, false, 0, false, 4, true, true, true>(l, in, out, begin, end, s);
-            case 1830408: return launch_st<float, 4, 4, 8, 5, false, 0, false, 4, true, true, true>(l, in, out, begin, end, s);
-            // the same, 5-row strips with stage 1's history in LDS (160 KB)
-            case 840508: return launch_st<float, 4, 5, 8, 5, false, 0, false, 4, true, true>(l, in, out, begin, end, s);
-            default: return launch_tkstrip_ilp(l, in, out, begin, end, 5, s);
-            }
-        }
+    if (steps < 3 || steps > 5) return set_error(STENCIL_EINVAL, "tkstrip steps must be 3, 4 or 5 (got %d)", steps);
+    const bool f32 = l.prob.dtype == STENCIL_F32;
+    auto run = [&](auto shape) { return launch_st<decltype(shape)>(l, in, out, begin, end, s); };
+    if (f32 && steps == 3) {
         switch (cfg) {
-        case 10608: return launch_st<double, 1, 6, 8, 5>(l, in, out, begin, end, s);
+        case 416: return run(Shape<float, 4, 4, 16, 3, kOneBuf>{});
+        case 808: return run(Shape<float, 4, 8, 8, 3>{});
+        case 20808: return run(Shape<float, 2, 8, 8, 3>{});
+        case 20608: return run(Shape<float, 2, 6, 8, 3>{});
+        }
+    } else if (f32 && steps == 4) {
+        switch (cfg) {
+        case 20808: return run(Shape<float, 2, 8, 8, 4>{});
+        case 404: return run(Shape<float, 4, 4, 8, 4>{});
+        }
+    } else if (f32) {
+        switch (cfg) {
+        case 20608: return run(Shape<float, 2, 6, 8, 5>{});
+        // stage 1's history in LDS (HL): 6-row strips (226 VGPRs); 7 rows with one boundary buffer (254)
+        case 820608: return run(Shape<float, 2, 6, 8, 5, kHistLds>{});
+        case 830708: return run(Shape<float, 2, 7, 8, 5, kOneBuf | kHistLds>{});
+        // the default shape from this file's build (AUTO takes the max-ILP build)
+        case 20508: return run(DefaultShape<float, 5>{});
+        // input planes loaded 3 / 4 planes ahead (NS = 5 / 6) instead of 2
+        case 520508: return run(Shape<float, 2, 5, 8, 5, 0, 5>{});
+        case 620508: return run(Shape<float, 2, 5, 8, 5, 0, 6>{});
+        // 4 cells per lane (256-wide regions: 16-B lane loads), one boundary-row buffer (80 KB of LDS)
+        case 40408: return run(Shape<float, 4, 4, 8, 5, kOneBuf>{});
+        case 840408: return run(Shape<float, 4, 4, 8, 5, kOneBuf | kHistLds>{});
+        // SPLIT (two strips per wave, 32 lanes x 4 cells: 16-B lane loads): 128 x 32 / 128 x 48 regions
+        case 1040208: return run(Shape<float, 4, 2, 8, 5, kSplit>{});
+        case 1040308: return run(Shape<float, 4, 3, 8, 5, kSplit>{});
+        case 1030308: return run(Shape<float, 4, 3, 8, 5, kOneBuf | kSplit>{});
+        case 1030212: return run(Shape<float, 4, 2, 12, 5, kOneBuf | kSplit>{});
+        case 1830308: return run(Shape<float, 4, 3, 8, 5, kOneBuf | kHistLds | kSplit>{});
+        case 1830408: return run(Shape<float, 4, 4, 8, 5, kOneBuf | kHistLds | kSplit>{});
+        // the same, 5-row strips with stage 1's history in LDS (160 KB)
+        case 840508: return run(Shape<float, 4, 5, 8, 5, kOneBuf | kHistLds>{});
+        }
+    } else if (steps == 3) {
+        switch (cfg) {
+        case 416: return run(Shape<double, 2, 4, 16, 3, kOneBuf>{});
+        case 10408: return run(Shape<double, 2, 4, 8, 3, kOneBuf>{});
+        case 608: return run(Shape<double, 2, 6, 8, 3>{});
+        case 216: return run(Shape<double, 2, 2, 16, 3, kOneBuf>{});
+        case 10808: return run(Shape<double, 1, 8, 8, 3>{});
+        case 10608: return run(Shape<double, 1, 6, 8, 3>{});
+#ifdef STENCIL_DIAG
+        // timing experiments only, results wrong on purpose: never in the product build
+        case 91: return run(Shape<double, 2, 4, 8, 3, 0, 4, 1>{});
+        case 92: return run(Shape<double, 2, 4, 8, 3, 0, 4, 2>{});
+        case 93: return run(Shape<double, 2, 4, 8, 3, 0, 4, 3>{});
+#endif
+        }
+    } else if (steps == 4) {
+        switch (cfg) {
+        case 10808: return run(Shape<double, 1, 8, 8, 4>{});
+        // the default shape from this file's build whatever the grid (AUTO takes the max-ILP build on
+        // packed-regime grids)
+        case 10708: return run(DefaultShape<double, 4>{});
+        case 10608: return run(Shape<double, 1, 6, 8, 4>{});
+        case 404: return run(Shape<double, 2, 4, 8, 4>{});
+        case 510708: return run(Shape<double, 1, 7, 8, 4, 0, 5>{});
+        // the default shape without the interior fast path (no duplicated step)
+        case 710708: return run(DefaultShape<double, 4, kNoFast>{});
+        case 510608: return run(Shape<double, 1, 6, 8, 4, 0, 5>{});
+        case 610608: return run(Shape<double, 1, 6, 8, 4, 0, 6>{});
+        case 610508: return run(Shape<double, 1, 5, 8, 4, 0, 6>{});
+        // stage 1's history in LDS (HL): 8-row strips at K = 4
+        case 810808: return run(Shape<double, 1, 8, 8, 4, kHistLds>{});
+        case 810708: return run(Shape<double, 1, 7, 8, 4, kHistLds>{});
+        // SPLIT (two strips per wave, 32 lanes x 2 cells: 16-B lane loads): 64 x 64 / 64 x 48 regions
+        case 1020408: return run(Shape<double, 2, 4, 8, 4, kSplit>{});
+        case 1020308: return run(Shape<double, 2, 3, 8, 4, kSplit>{});
+        case 1820408: return run(Shape<double, 2, 4, 8, 4, kOneBuf | kHistLds | kSplit>{});
+        // 9-row strips without the fast path: 72 rows for 64 output rows (512 = 8 x 64)
+        case 820908: return run(Shape<double, 1, 9, 8, 4, kNoFast | kHistLds>{});
+        }
+    } else {
+        switch (cfg) {
+        case 10608: return run(Shape<double, 1, 6, 8, 5>{});
         // stage 1's history in LDS (HL): 7- and 8-row strips at K = 5
-        case 810708: return launch_st<double, 1, 7, 8, 5, true, 0, false, 4, true, true>(l, in, out, begin, end, s);
-        case 810608: return launch_st<double, 1, 6, 8, 5, true, 0, false, 4, true, true>(l, in, out, begin, end, s);
+        case 810708: return run(Shape<double, 1, 7, 8, 5, kHistLds>{});
+        case 810608: return run(Shape<double, 1, 6, 8, 5, kHistLds>{});
         // + one boundary-row buffer (a second barrier per step) and no fast path: 7 rows fit (254 VGPRs)
-        case 830708: return launch_st<double, 1, 7, 8, 5, false, 0, false, 4, false, true>(l, in, out, begin, end, s);
-        default: return launch_st<double, 1, 5, 8, 5>(l, in, out, begin, end, s);
+        case 830708: return run(Shape<double, 1, 7, 8, 5, kOneBuf | kNoFast | kHistLds>{});
         }
     }
-    return set_error(STENCIL_EINVAL, "tkstrip steps must be 3, 4 or 5 (got %d)", steps);
+    // The default shape.  Two of them run from the max-ILP build (kernels_strip_ilp.hip): the fp64 K = 4
+    // strip on grids of at most 2 tiles per CU slot (packed schedule, fast path), the fp32 K = 5 strip always.
+    if (!f32 && steps == 4 && packed_regime<DefaultShape<double, 4>>(l))
+        return launch_tkstrip_ilp(l, in, out, begin, end, 4, s);
+    if (f32 && steps == 5) return launch_tkstrip_ilp(l, in, out, begin, end, 5, s);
+    return launch_default<0>(l, in, out, begin, end, steps, s, StripExtras{}, "tkstrip");
 }
 
-// The default shapes with face signalling (stencil_sweepk_signal).
-int launch_tkstrip_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
-                          unsigned* sig, unsigned long long* fsig, int* nsig, hipStream_t s, const StripGate& gate) {
+// The default shapes with the extras' options (common.hpp): face signalling (stencil_sweepk_signal), the
+// update maximum (stencil_sweepk_update_max; UMAX above the kernel), or both.
+int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
+                           const StripExtras& x, hipStream_t s) {
+    const bool umax = x.umax != nullptr;
+    if (!x.signal && !umax) return set_error(STENCIL_EINVAL, "neither a face-signalled nor a checking launch");
+    const char* const what = !umax ? "face-signalled sweeps"
+                                   : (x.signal ? "face-signalled update-max sweeps" : "update-max sweeps");
     if (!temporal2_supports(l.prob))
-        return set_error(STENCIL_EUNSUPPORTED, "face-signalled sweeps cover the 3D r=1 naive 7-point star only");
-    if (l.prob.dtype == STENCIL_F32) {
-        switch (steps) {
-        case 3: return launch_st<float, 4, 4, 8, 3, true, 0, true>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 4: return launch_st<float, 2, 7, 8, 4, true, 0, true>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 5: return launch_st<float, 2, 5, 8, 5, true, 0, true>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        default: break;
-        }
-    } else {
-        switch (steps) {
-        case 3: return launch_st<double, 2, 4, 8, 3, true, 0, true>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 4: return launch_st<double, 1, 7, 8, 4, true, 0, true>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 5: return launch_st<double, 1, 5, 8, 5, true, 0, true>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        default: break;
-        }
-    }
-    return set_error(STENCIL_EINVAL, "face-signalled sweeps: steps must be 3, 4 or 5 (got %d)", steps);
-}
-
-// The default shapes reporting max |u^K - u^(K-1)| over the cells they store
-// (stencil_sweepk_update_max; UMAX above): plain launches through launch_st,
-// `word` travels in the kernel's fsig argument.  launch_tkstrip_signal's six
-// shapes, but for fp32 K = 4 (below).  DESIGN.md §5.6 has the resource table.
-int launch_tkstrip_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
-                              unsigned long long* word, hipStream_t s) {
-    if (!temporal2_supports(l.prob))
-        return set_error(STENCIL_EUNSUPPORTED, "update-max sweeps cover the 3D r=1 naive 7-point star only");
-    if (!word) return set_error(STENCIL_EINVAL, "null update_max_bits");
-    constexpr bool U = true;
-    if (l.prob.dtype == STENCIL_F32) {
-        switch (steps) {
-        case 3: return launch_st<float, 4, 4, 8, 3, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
-        // 6-row strips: the default 7-row shape (253 VGPRs) spills a VGPR once it holds the accumulator
-        // (8 B of scratch per lane); 6 rows take 223 and none.  Bitwise the same sweep (120 x 40 tiles).
-        case 4: return launch_st<float, 2, 6, 8, 4, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
-        case 5: return launch_st<float, 2, 5, 8, 5, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
-        default: break;
-        }
-    } else {
-        switch (steps) {
-        case 3: return launch_st<double, 2, 4, 8, 3, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
-        case 4: return launch_st<double, 1, 7, 8, 4, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
-        case 5: return launch_st<double, 1, 5, 8, 5, true, 0, false, 4, true, false, false, U>(l, in, out, begin, end, s, nullptr, nullptr, word);
-        default: break;
-        }
-    }
-    return set_error(STENCIL_EINVAL, "update-max sweeps: steps must be 3, 4 or 5 (got %d)", steps);
-}
-
-// The face-signalled default shapes that also report their update
-// (stencil_sweepk_signal_update_max; SIG + UMAX above): launch_tkstrip_signal's
-// launches with the word in gate.umax.  fp32 K = 4 runs 6-row strips, as the
-// plain checking launch does (the 7-row shape has no VGPR left for the
-// accumulator).  DESIGN.md §5.6 has the resource table.
-int launch_tkstrip_signal_update_max(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
-                                     int steps, unsigned* sig, unsigned long long* fsig, unsigned long long* word,
-                                     int* nsig, hipStream_t s, const StripGate& gate_in) {
-    if (!temporal2_supports(l.prob))
-        return set_error(STENCIL_EUNSUPPORTED, "face-signalled update-max sweeps cover the 3D r=1 naive 7-point star only");
-    if (!word) return set_error(STENCIL_EINVAL, "null update_max_bits");
-    StripGate gate = gate_in;
-    gate.umax = word;
-    constexpr bool U = true;
-    if (l.prob.dtype == STENCIL_F32) {
-        switch (steps) {
-        case 3: return launch_st<float, 4, 4, 8, 3, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 4: return launch_st<float, 2, 6, 8, 4, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 5: return launch_st<float, 2, 5, 8, 5, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        default: break;
-        }
-    } else {
-        switch (steps) {
-        case 3: return launch_st<double, 2, 4, 8, 3, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        // 6-row strips here too: the plain signalled 7-row shape already spills (52 B of scratch per lane),
-        // with the accumulator 80 B; 6 rows take none.  Bitwise the same sweep (64 x 40 tiles).
-        case 4: return launch_st<double, 1, 6, 8, 4, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        case 5: return launch_st<double, 1, 5, 8, 5, true, 0, true, 4, true, false, false, U>(l, in, out, begin, end, s, sig, nsig, fsig, gate);
-        default: break;
-        }
-    }
-    return set_error(STENCIL_EINVAL, "face-signalled update-max sweeps: steps must be 3, 4 or 5 (got %d)", steps);
+        return set_error(STENCIL_EUNSUPPORTED, "%s cover the 3D r=1 naive 7-point star only", what);
+    if (!x.signal) return launch_default<kUmax>(l, in, out, begin, end, steps, s, x, what);
+    return umax ? launch_default<kSig | kUmax>(l, in, out, begin, end, steps, s, x, what)
+                : launch_default<kSig>(l, in, out, begin, end, steps, s, x, what);
 }
 
 #endif  // STRIP_ILP_TU
