@@ -56,6 +56,8 @@ $(OBJ)/knobs_debug.o: stencil_amd/csrc/knobs.cpp stencil_amd/csrc/common.hpp inc
 # flag goes to the device compilation only (the host x86 backend has no such scheduler)
 $(OBJ)/kernels_strip_ilp.o: stencil_amd/csrc/kernels_strip.hip
 $(OBJ)/kernels_strip_ilp.o: HIPFLAGS += -Xarch_device -mllvm=-misched=gcn-max-ilp
+# the strip kernel's source shapes (kernels_strip_source.hip includes kernels_strip.hip), default scheduler
+$(OBJ)/kernels_strip_source.o: stencil_amd/csrc/kernels_strip.hip
 # the strip probe (debug library only): the max-ILP shapes again, as a compile-time variant
 $(OBJ)/kernels_strip_probe.o: stencil_amd/csrc/kernels_strip.hip
 $(OBJ)/kernels_strip_probe.o: HIPFLAGS += -Xarch_device -mllvm=-misched=gcn-max-ilp

@@ -460,6 +460,49 @@ int stencil_iterate_until(const stencil_layout* l, void* a, void* b, uint32_t ma
 int stencil_until_plan(const stencil_layout* l, uint32_t block, int32_t norm, int64_t* launches,
                        int32_t* fused_check);
 
+/* Sweeps with a source term (Poisson's right-hand side, a heat source, a
+ * multigrid smoother): u' = S(u) + g.  Scope: the 3D 7-point star, r = 1,
+ * naive order, fp32 / fp64, layouts with flags == 0, kernel AUTO or TEMPORALK.
+ * `src` is a device grid of the SAME layout as the field (stencil_alloc,
+ * stencil_upload); only its interior cells have meaning, the caller scales it
+ * (g = h^2 / 6 f for the 7-point Laplacian).  One source sweep over planes
+ * [begin, end) stores, at every interior cell c of those planes,
+ *   out(c) = fl( fl( sum6(in, c) * avg ) + src(c) )
+ * with sum6 and avg the plain sweep's (0 + x- + x+ + y- + y+ + z- + z+): the
+ * multiply is rounded, then the source is added and rounded again -- never one
+ * fma.  A launch of `steps` sweeps is bitwise `steps` such sweeps (ghost cells
+ * keep their input value in between and get no source).  It stores the
+ * interior cells of [begin, end) of `out` and nothing else, never stores to
+ * `in` or `src`, and no value of a `src` ghost cell, padding or tail-pad
+ * element reaches a result.
+ *
+ * stencil_sweepk_source: steps in 1 .. STENCIL_SOURCE_MAX_STEPS; 2, 3 and 4 are
+ * the K-step strip kernel with its source option (one extra read stream per
+ * launch: 24 B per cell and launch in fp64 instead of 16), 1 a single sweep.
+ * stencil_iterate_source: stencil_iterate with the source -- ping-pong from
+ * `a` in launches of STENCIL_SOURCE_MAX_STEPS sweeps, the remainder as one
+ * shorter launch; read *final_in_b.  stencil_source_plan (host only, no
+ * device): the kernel launches of that job and the sweeps of its fused launch.
+ * stencil_iterate_until_source: stencil_iterate_until's stopping rule,
+ * arguments, outputs and edge cases on source sweeps, always with the un-fused
+ * check: block - 1 sweeps by stencil_iterate_source's plan, one single source
+ * sweep, then stencil_diff_norms' kernels.
+ * STENCIL_EINVAL: NULL src; src equal to in, out, a or b; a == b or NULL
+ * grids; a bad range; steps outside 1 .. STENCIL_SOURCE_MAX_STEPS;
+ * check_every = 0; tol < 0 or NaN; an unknown norm.  STENCIL_EUNSUPPORTED
+ * (the message names the restriction): 2D, the box, r > 1, the DMA order,
+ * halo flags, a forced kernel family other than AUTO or TEMPORALK. */
+#define STENCIL_SOURCE_MAX_STEPS 4
+int stencil_sweepk_source(const stencil_layout* l, const void* in, void* out, const void* src,
+                          int64_t begin, int64_t end, int32_t steps, void* stream);
+int stencil_iterate_source(const stencil_layout* l, void* a, void* b, const void* src, uint32_t iterations,
+                           void* stream, int* final_in_b, float* elapsed_ms);
+int stencil_source_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches, int32_t* steps);
+int stencil_iterate_until_source(const stencil_layout* l, void* a, void* b, const void* src,
+                                 uint32_t max_iterations, uint32_t check_every, int32_t norm, double tol,
+                                 void* stream, uint32_t* iterations_done, int* final_in_b,
+                                 double* last_norm, int* converged, float* elapsed_ms);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,

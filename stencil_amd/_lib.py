@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "stencil_sweepk_update_max", "stencil_until_plan",
     "stencil_sweepk_signal_update_max", "stencil_sweepk_signal_update_max_gated",
     "stencil_slab_run_until", "stencil_slab_until_plan",
+    "stencil_sweepk_source", "stencil_iterate_source", "stencil_source_plan", "stencil_iterate_until_source",
 )
 
 
@@ -175,6 +176,13 @@ def signatures() -> dict:
                                           POINTER(c_float)]),
         "stencil_sweepk_update_max": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
         "stencil_until_plan": (c_int, [L, c_uint32, c_int32, POINTER(c_int64), POINTER(c_int32)]),
+        "stencil_sweepk_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
+        "stencil_iterate_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, POINTER(c_int),
+                                           POINTER(c_float)]),
+        "stencil_source_plan": (c_int, [L, c_uint32, POINTER(c_int64), POINTER(c_int32)]),
+        "stencil_iterate_until_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int32, c_double,
+                                                 c_void_p, POINTER(c_uint32), POINTER(c_int), POINTER(c_double),
+                                                 POINTER(c_int), POINTER(c_float)]),
         "stencil_sweepk_geometry": (c_int, [L, c_int64, c_int64, c_int32, POINTER(c_int64), POINTER(c_int32),
                                             POINTER(c_int32)]),
         "stencil_sweepk_signal": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,

@@ -1324,6 +1324,178 @@ int stencil_until_plan(const stencil_layout* l, uint32_t block, int32_t norm, in
     return STENCIL_OK;
 }
 
+// ---- sweeps with a source term (include/stencil_hip.h) ----
+}  // extern "C"
+
+namespace stencil {
+namespace {
+
+// The problems the source sweeps cover; the message names what rules one out.
+int check_source_problem(const stencil_layout* l) {
+    if (int rc = check_layout(l)) return rc;
+    const stencil_problem& p = l->prob;
+    if (p.dims != 3) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: 3D grids only (got dims = %d)", p.dims);
+    if (p.shape != STENCIL_STAR) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: the 7-point star only, not the box");
+    if (p.radius != 1) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: radius 1 only (got %d)", p.radius);
+    if (p.order != STENCIL_ORDER_NAIVE) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: the naive sum order only, not DMA");
+    if (p.flags != 0) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: layouts without halo flags only (got %d)", p.flags);
+    if (p.kernel != STENCIL_KERNEL_AUTO && p.kernel != STENCIL_KERNEL_TEMPORALK)
+        return set_error(STENCIL_EUNSUPPORTED, "source sweeps: kernel AUTO or TEMPORALK only (got %d)", p.kernel);
+    return STENCIL_OK;
+}
+
+// `steps` source sweeps in -> out over [begin, end): the single sweep, or the strip kernel's source shapes
+int launch_source(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
+                  int steps, hipStream_t s) {
+    return steps == 1 ? launch_source1(l, in, out, src, begin, end, s)
+                      : launch_tkstrip_source(l, in, out, src, begin, end, steps, s);
+}
+
+int check_source_job(const stencil_layout* l, const void* a, const void* b, const void* src) {
+    if (int rc = check_source_problem(l)) return rc;
+    if (!a || !b || a == b) return set_error(STENCIL_EINVAL, "need two distinct grids");
+    if (!src) return set_error(STENCIL_EINVAL, "null source grid");
+    if (src == a || src == b) return set_error(STENCIL_EINVAL, "the source grid must not be one of the field's grids");
+    return STENCIL_OK;
+}
+
+}  // namespace
+}  // namespace stencil
+
+extern "C" {
+
+int stencil_sweepk_source(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                          int64_t end, int32_t steps, void* stream) {
+    if (int rc = check_source_problem(l)) return rc;
+    if (!in || !out) return set_error(STENCIL_EINVAL, "null grid");
+    if (!src) return set_error(STENCIL_EINVAL, "null source grid");
+    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
+    if (src == in || src == out) return set_error(STENCIL_EINVAL, "the source grid must not be one of the field's grids");
+    if (steps < 1 || steps > kSourceSteps)
+        return set_error(STENCIL_EINVAL, "steps must be 1..%d (got %d)", kSourceSteps, steps);
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
+    const int rc = launch_source(*l, in, out, src, begin, end, steps, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+int stencil_source_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches, int32_t* steps) {
+    if (int rc = check_source_problem(l)) return rc;
+    if (launches) *launches = int64_t(iterations / kSourceSteps) + (iterations % kSourceSteps ? 1 : 0);
+    if (steps) *steps = kSourceSteps;
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_iterate_source(const stencil_layout* l, void* a, void* b, const void* src, uint32_t iterations,
+                           void* stream, int* final_in_b, float* elapsed_ms) {
+    if (int rc = check_source_job(l, a, b, src)) return rc;
+    hipStream_t s = as_stream(stream);
+    const SustainedScope sustained(iterations >= kSustainedSweeps);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (elapsed_ms) {
+        STENCIL_HIP_CHECK(hipEventCreate(&e0));
+        STENCIL_HIP_CHECK(hipEventCreate(&e1));
+        STENCIL_HIP_CHECK(hipEventRecord(e0, s));
+    }
+    const int64_t n = stencil_slow_extent(l);
+    void* in = a;
+    void* out = b;
+    int rc = STENCIL_OK;
+    // fused launches of kSourceSteps sweeps, then the remainder as one shorter launch
+    for (uint32_t i = 0; i < iterations && rc == STENCIL_OK;) {
+        const uint32_t k = std::min<uint32_t>(kSourceSteps, iterations - i);
+        rc = launch_source(*l, in, out, src, 0, n, int(k), s);
+        std::swap(in, out);
+        i += k;
+    }
+    if (elapsed_ms) {
+        if (rc == STENCIL_OK) {
+            hipError_t e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            if (e == hipSuccess) e = hipEventElapsedTime(elapsed_ms, e0, e1);
+            if (e != hipSuccess) rc = set_error(STENCIL_EHIP, "source job timing: %s", hipGetErrorString(e));
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    if (rc != STENCIL_OK) return rc;
+    if (final_in_b) *final_in_b = in == b ? 1 : 0;
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_iterate_until_source(const stencil_layout* l, void* a, void* b, const void* src, uint32_t max_iterations,
+                                 uint32_t check_every, int32_t norm, double tol, void* stream,
+                                 uint32_t* iterations_done, int* final_in_b, double* last_norm, int* converged,
+                                 float* elapsed_ms) {
+    if (int rc = check_source_job(l, a, b, src)) return rc;
+    if (check_every == 0) return set_error(STENCIL_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0.0)) return set_error(STENCIL_EINVAL, "tol must be a number >= 0");
+    if (norm != STENCIL_NORM_MAX && norm != STENCIL_NORM_L2) return set_error(STENCIL_EINVAL, "bad norm %d", norm);
+    hipStream_t s = as_stream(stream);
+    const int64_t n = stencil_slow_extent(l);
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    NormScratch sc;
+    sc.s = s;
+    std::vector<double> host(size_t(2 * n));
+    uint32_t done = 0;
+    int conv = 0;
+    double last = std::numeric_limits<double>::infinity();
+    void* cur = a;  // the grid that holds the newest sweep
+    void* old = b;
+    if (max_iterations > 0) {
+        if (elapsed_ms) {
+            STENCIL_HIP_CHECK(hipEventCreate(&ev.e0));
+            STENCIL_HIP_CHECK(hipEventCreate(&ev.e1));
+            STENCIL_HIP_CHECK(hipEventRecord(ev.e0, s));
+        }
+        if (n > 0)
+            STENCIL_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sc.dev), size_t(diff_norms_workspace_bytes(*l, n)), s));
+    }
+    while (done < max_iterations) {
+        // block - 1 sweeps by stencil_iterate_source's plan, then one single source sweep, so that the
+        // grids hold u^(n-1) and u^n for the check (stencil_iterate_until's un-fused form)
+        const uint32_t block = std::min(check_every, max_iterations - done);
+        if (block > 1) {
+            int fin = 0;
+            if (int rc = stencil_iterate_source(l, cur, old, src, block - 1, stream, &fin, nullptr)) return rc;
+            if (fin) std::swap(cur, old);
+        }
+        if (int rc = launch_source(*l, cur, old, src, 0, n, 1, s)) return rc;
+        std::swap(cur, old);
+        done += block;
+        if (int rc = norms_to_host(*l, cur, old, 0, n, sc.dev, host.data(), s)) return rc;
+        last = scalar_norm(host.data(), n, norm);
+        if (last <= tol) {
+            conv = 1;
+            break;
+        }
+        if (last != last) break;
+    }
+    if (elapsed_ms) {
+        *elapsed_ms = 0.f;
+        if (ev.e0) {
+            STENCIL_HIP_CHECK(hipEventRecord(ev.e1, s));
+            STENCIL_HIP_CHECK(hipEventSynchronize(ev.e1));
+            STENCIL_HIP_CHECK(hipEventElapsedTime(elapsed_ms, ev.e0, ev.e1));
+        }
+    }
+    if (iterations_done) *iterations_done = done;
+    if (final_in_b) *final_in_b = cur == b ? 1 : 0;
+    if (last_norm) *last_norm = last;
+    if (converged) *converged = conv;
+    clear_error();
+    return STENCIL_OK;
+}
+
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream, float* elapsed_ms) {
     if (!dst || !src || bytes <= 0 || (bytes % 16) != 0 || reps <= 0) return set_error(STENCIL_EINVAL, "bad copy args");
     hipStream_t s = as_stream(stream);

@@ -192,6 +192,14 @@ int launch_tkstrip_ilp(const stencil_layout& l, const void* in, void* out, int64
 // built as a compile-time variant, debug cfg 97
 int launch_tkstrip_probe(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                          hipStream_t s);
+// kernels_strip_source.hip: `steps` (2..4) fused sweeps that each add the source grid `src` (the field's
+// layout) after the averaging: stencil_sweepk_source's fused launches.  kSourceSteps: the most it fuses.
+constexpr int kSourceSteps = 4;
+int launch_tkstrip_source(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                          int64_t end, int steps, hipStream_t s);
+// kernels_source.hip: one sweep with the source added
+int launch_source1(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
+                   hipStream_t s);
 // The halo gate of a face-signalled launch (stencil_sweepk_signal_gated):
 // the workgroups whose z range reaches a halo plane first wait until *word
 // (the slab's exchange-completion word, stencil_exchange_done) has reached
@@ -218,6 +226,7 @@ struct StripExtras {
     unsigned long long* umax = nullptr;
     StripGate gate;                      // signal: the halo gate (a null word: none)
     int* nsig = nullptr;                 // signal, out: the adds per face (one per tile)
+    const void* src = nullptr;           // source launches (kSrc shapes): the source grid, the field's layout
 };
 // The default strip shapes with at least one of the extras' options
 int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,

@@ -27,6 +27,15 @@ void report_convergence(std::string_view method_name, ProgramOptions const& opti
     if (!stencil.converged() && g_status == 0) g_status = 5;
 }
 
+// With --source: one extra line of a run, the final interior's sum (exact: every digit of the double).
+void report_source(std::string_view method_name, ProgramOptions const& options, Stencil const& stencil) {
+    if (!options.has_source) return;
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.17g", stencil.interior_sum());
+    std::cout << "[stencil-amd] " << method_name << ": source " << options.source << ", " << stencil.sweeps()
+              << " sweeps, interior sum = " << buf << "\n";
+}
+
 void run_test(std::string_view method_name, ProgramOptions const& options) {
     if (options.check_result) {
         std::cout << "Start to check the correctness of method " << method_name << ".\n";
@@ -38,6 +47,7 @@ void run_test(std::string_view method_name, ProgramOptions const& options) {
             return;
         }
         report_convergence(method_name, options, stencil);
+        report_source(method_name, options, stencil);
 
         if (stencil.check_result()) {
             std::cout << "The results of method " << method_name << " is correct.\n";
@@ -76,6 +86,7 @@ void run_test(std::string_view method_name, ProgramOptions const& options) {
                   << static_cast<std::chrono::duration<double, std::milli>>(*duration).count() << "ms for "
                   << options.iterations << " iterations.\n";
         report_convergence(method_name, options, stencil);
+        report_source(method_name, options, stencil);
         total_sweeps += stencil.sweeps();
     }
 
@@ -119,7 +130,9 @@ int main(int argc, char** argv) {
             std::cout << " tol=";
             if (options->until()) std::cout << options->tol;
             else std::cout << "off";
-            std::cout << " check_every=" << options->check_every << " norm=" << (options->norm_l2 ? "l2" : "max") << "\n";
+            std::cout << " check_every=" << options->check_every << " norm=" << (options->norm_l2 ? "l2" : "max");
+            if (options->has_source) std::cout << " source=" << options->source;
+            std::cout << "\n";
             return 0;
         }
         try {

@@ -150,6 +150,8 @@ auto ProgramOptions::parse(int argc, char** argv) -> std::optional<ProgramOption
          [&](const std::string& v) { return parse_unsigned(v, r.check_every) && r.check_every >= 1; }},
         {0, "norm", Kind::Str, false, "[ext] Norm of the update --tol compares: max (default) or l2.",
          [&](const std::string& v) { if (v != "max" && v != "l2") return false; r.norm_l2 = v == "l2"; return true; }},
+        {0, "source", Kind::Double, false, "[ext] Add X at every interior cell after each sweep (--dims 3; methods HIP, CPU).",
+         [&](const std::string& v) { if (!parse_double(v, r.source)) return false; r.has_source = true; return true; }},
     };
 
     auto find_long = [&](const std::string& n) -> Opt* {
@@ -213,5 +215,14 @@ auto ProgramOptions::parse(int argc, char** argv) -> std::optional<ProgramOption
     }
     for (const Opt& o : opts)
         if (o.required && !o.seen) return fail("--" + std::string(o.longname) + " is required");
+    if (r.has_source) {
+        // the source sweeps cover the 3D 7-point star on one GPU (stencil_iterate_source) and the CPU loop
+        if (r.dims != 3) return fail("--source needs a 3D grid (--dims 3)");
+        if (r.box || r.radius != 1) return fail("--source covers the 7-point star only (--shape star, -r 1)");
+        if (r.gpus != 1) return fail("--source runs on one GPU (no --gpus)");
+        if (r.kernel != "auto" && r.kernel != "temporalk") return fail("--source needs --kernel auto or temporalk");
+        for (const std::string& m : r.method_names)
+            if (m != "HIP" && m != "CPU") return fail("--source is valid with the methods HIP and CPU only (got " + m + ")");
+    }
     return r;
 }

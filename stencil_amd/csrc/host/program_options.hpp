@@ -45,6 +45,8 @@ struct ProgramOptions {
     double tol = -1.0;             // --tol X (>= 0): sweep until one sweep's update is <= X, -i is the cap; < 0 = off
     unsigned check_every = 100;    // --check-every N (>= 1): sweeps between two checks
     bool norm_l2 = false;          // --norm max|l2: the norm of the update
+    bool has_source = false;       // --source VALUE: a constant added at every interior cell after each sweep
+    double source = 0.0;           //   (u' = S(u) + VALUE; --dims 3, methods HIP and CPU)
 
     bool until() const { return tol >= 0.0; }
 

@@ -42,9 +42,11 @@ void u01(uint64_t u, double& d) { d = double(u >> 11) * 0x1.0p-53; }
 struct DeviceGrids {
     void* a = nullptr;
     void* b = nullptr;
+    void* src = nullptr;  // --source: the source grid
     ~DeviceGrids() {
         if (a) stencil_free(a);
         if (b) stencil_free(b);
+        if (src) stencil_free(src);
     }
 };
 
@@ -213,6 +215,15 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     check(stencil_alloc(&l, &d.b), "stencil_alloc");
     upload(d.a, matrix);
     upload(d.b, result);
+    if (options.has_source) {
+        // the constant at every interior cell (only those have meaning), zeros around them
+        BoundaryGrid<T> g(options.dims, matrix.width(), matrix.height(), matrix.depth(), options.radius);
+        for (int64_t z = 0; z < g.depth(); ++z)
+            for (int64_t y = 0; y < g.height(); ++y)
+                for (int64_t x = 0; x < g.width(); ++x) g.elem_at(z, y, x) = T(options.source);
+        check(stencil_alloc(&l, &d.src), "stencil_alloc");
+        check(stencil_upload(&l, d.src, g.data(), g.row_stride(), g.rows_with_boundary(), nullptr), "upload");
+    }
     check(stencil_synchronize(nullptr), "synchronize");
 
     // Untimed warm-up: the first launch of a kernel in a process pays HIP's
@@ -221,6 +232,9 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     if (options.iterations > 0) {
         int fin = 0;
         check(stencil_iterate(&l, d.a, d.b, 1, nullptr, &fin, nullptr), "warm-up");
+        // the source job's launches (the fused ones with their schedule choices, the single sweep)
+        if (options.has_source)
+            for (uint32_t n : {7u, 2u, 1u}) check(stencil_iterate_source(&l, d.a, d.b, d.src, n, nullptr, &fin, nullptr), "warm-up");
         // and the per-shape z-chunk schedule choice, timed on a shape's first
         // fused launch (kernels_strip.hip pick_schedule)
         check(stencil_prepare(&l, d.a, d.b, nullptr), "warm-up");
@@ -238,7 +252,19 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     int final_in_b = 0;
     float ms = 0.f;
     auto const start = std::chrono::steady_clock::now();
-    if (options.until()) {
+    if (options.has_source && options.until()) {
+        uint32_t done = 0;
+        int conv = 0;
+        check(stencil_iterate_until_source(&l, d.a, d.b, d.src, options.iterations, options.check_every,
+                                           options.norm_l2 ? STENCIL_NORM_L2 : STENCIL_NORM_MAX, options.tol, nullptr,
+                                           &done, &final_in_b, &run_norm, &conv, &ms),
+              "stencil_iterate_until_source");
+        sweeps_done = done;
+        run_converged = conv != 0;
+    } else if (options.has_source) {
+        check(stencil_iterate_source(&l, d.a, d.b, d.src, options.iterations, nullptr, &final_in_b, &ms),
+              "stencil_iterate_source");
+    } else if (options.until()) {
         // -i is the cap: sweep until one sweep's update is <= --tol
         uint32_t done = 0;
         int conv = 0;
@@ -357,7 +383,9 @@ bool Stencil::naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iter
                             for (int k = 1; k <= r; ++k) sum += src[c + k * sxy];
                         }
                     }
-                    dst[c] = sum * avg;
+                    const T avged = sum * avg;
+                    // --source: a second rounding after the multiply's, never one fma (built with -ffp-contract=off)
+                    dst[c] = options.has_source ? avged + T(options.source) : avged;
                 }
         std::swap(in, out);
         swapped = !swapped;
@@ -442,6 +470,21 @@ bool Stencil::check_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& 
                 }
             }
     return true;
+}
+
+// The final grid's interior added up in double, ascending z, y, x: one number that names the result exactly.
+template <class T>
+double Stencil::sum_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const {
+    const BoundaryGrid<T>& g = (sweeps() & 1u) ? result : matrix;
+    double s = 0.0;
+    for (int64_t z = 0; z < g.depth(); ++z)
+        for (int64_t y = 0; y < g.height(); ++y)
+            for (int64_t x = 0; x < g.width(); ++x) s += double(g.elem_at(z, y, x));
+    return s;
+}
+
+auto Stencil::interior_sum() const -> double {
+    return options.fp64 ? sum_typed(matrix64, result64) : sum_typed(matrix32, result32);
 }
 
 auto Stencil::check_result() const -> bool {

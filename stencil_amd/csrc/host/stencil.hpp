@@ -45,6 +45,8 @@ public:
     auto run(std::string_view method_name) -> std::optional<std::chrono::steady_clock::duration>;
 
     auto check_result() const -> bool;
+    /// The last run's final interior added up in double in ascending z, y, x order.
+    auto interior_sum() const -> double;
 
     /// Write the final grid of the last run as a 24-bit BMP (2D: the grid;
     /// 3D: the middle z plane), colour map of stencil.cpp:153-188.
@@ -76,6 +78,8 @@ private:
     auto run_slabs(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) -> std::chrono::steady_clock::duration;
     template <class T>
     bool check_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const;
+    template <class T>
+    double sum_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const;
     template <class T>
     bool naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iterations) const;
     template <class T>

@@ -91,6 +91,12 @@
 #define TK_XRING8 0
 #endif
 
+// kernels_strip_ilp.hip, kernels_strip_probe.hip and kernels_strip_source.hip compile this file again for
+// a few instantiations of their own: the kernel and launch_st, not the host-side schedule code
+#if defined(STRIP_ILP_TU) || defined(STRIP_SOURCE_TU)
+#define STRIP_EXTRA_TU
+#endif
+
 namespace stencil {
 namespace {
 
@@ -280,13 +286,27 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // whichever way the chunk is walked.  The face adds touch no LDS and their
 // barrier is workgroup-uniform, so the reduction below (behind a barrier of
 // its own) still finds the boundary rows free.
+// SRC (stencil_sweepk_source): every stage adds a source term,
+// t_s(q) = fl(fl(sum6 * avg) + rhs(q)) at interior cells -- the multiply is
+// rounded first, the add is a second rounding, never one fma.  `rhs` is a grid
+// of the field's layout, so a lane's row offsets off[k] serve it too and only
+// the per-plane base differs.  Stage s of step p needs rhs(p-s): K planes per
+// step, each used at K consecutive steps, so they live in a register ring of
+// NR = K + 1 slots (K + 2 when that is odd, so the unrolled loop stays at LCM
+// steps): slot (q - p0) % NR holds rhs(q), and the slot of rhs(p-K), consumed
+// at step p, takes the load of rhs(p-K+NR) -- issued with in(p+2), at least two
+// steps before its first use.  Loads are clamped like the input's (the same
+// planes exist in both allocations); what a clamped or ghost address returns
+// is dropped by the ghost-cell selects (s < K) or never stored (s = K), and the
+// select-free segments compute such cells only in planes that never reach the
+// output.
 template <typename T, int V, int RY, int NW, int K, bool DB, int DIAG = 0, bool SIG = false, int NS = 4, bool FP = true,
-          bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false>
+          bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false, bool SRC = false>
 __global__ void __launch_bounds__(64 * NW)
     tkstrip_7pt(const T* __restrict__ in, T* __restrict__ out, Geom g, int zbeg, int zend, int zchunk,
                 int tiles_x, int tiles_y, int halo_lo, int halo_hi, T avg, unsigned* __restrict__ sig,
                 unsigned long long* __restrict__ fsig, const int* __restrict__ sched, int fast, int xcd_pw,
-                TierArgs tier, StripGate gate) {
+                TierArgs tier, StripGate gate, const T* __restrict__ rhs) {
     using Tl = StripTile<T, V, RY, NW, K, DB, SPLIT>;
     using VT = typename VecS<T, V>::type;
     constexpr int XR = Tl::XR, TX = Tl::TX, TY = Tl::TY, RH = Tl::RH, RW = Tl::RW, NB = Tl::NB;
@@ -294,6 +314,9 @@ __global__ void __launch_bounds__(64 * NW)
     static_assert(!SPLIT || !TIER, "SPLIT: plain or face-signalled launches");
     static_assert(!UMAX || (!TIER && DIAG == 0 && !TK_SST && !TK_XRING8 && !TK_PROBE_NOBAR),
                   "UMAX: plain or face-signalled launches of the product shapes only");
+    static_assert(!SRC || (!SIG && !TIER && !UMAX && !HL && !SPLIT && DIAG == 0 && NS == 4 && !TK_SST && !TK_XRING8 &&
+                           !TK_PROBE_NOBAR),
+                  "SRC: plain launches of the source shapes only");
     constexpr bool SST = Tl::SSTS && !SIG && !TIER && !HL;
     constexpr int NI = (RY + 1) / 2;  // SST: row pairs per strip
     typedef T V4T __attribute__((ext_vector_type(4)));
@@ -373,6 +396,7 @@ __global__ void __launch_bounds__(64 * NW)
     const int64_t bias = g.row + XR * V;
     const char* __restrict__ src = reinterpret_cast<const char*>(in + g.origin - bias);
     char* __restrict__ dst = reinterpret_cast<char*>(out + g.origin - bias);
+    const char* __restrict__ rsrc = SRC ? reinterpret_cast<const char*>(rhs + g.origin - bias) : nullptr;
 
     {
         constexpr int N16 = int(Tl::lds_bytes / 16);
@@ -525,11 +549,23 @@ __global__ void __launch_bounds__(64 * NW)
             }
         }
     };
+    // SRC: one plane of the source grid, clamped like the input's
+    auto load_rhs = [&](VT (&d)[RY], int z) {
+        const int zz = z < zfirst ? zfirst : (z > zlast ? zlast : z);
+        const char* base = rsrc + int64_t(zz) * plane * int64_t(sizeof(T));
+#pragma unroll
+        for (int k = 0; k < RY; ++k) d[k] = *reinterpret_cast<const VT*>(base + off[k]);
+    };
     static_assert(NS >= 4, "the input ring holds in(p-2) .. in(p+1) at least");
-    constexpr int LCM = NS % 2 == 0 ? NS : 2 * NS;  // steps until ring slot and H parity repeat
+    constexpr int NR = (K + 1) % 2 == 0 ? K + 1 : K + 2;  // SRC: source planes in registers
+    constexpr int LCM0 = NS % 2 == 0 ? NS : 2 * NS;
+    // steps until ring slot and H parity (SRC: and the source ring's slot) repeat
+    constexpr int LCM = !SRC || LCM0 % NR == 0 ? LCM0 : (NR % LCM0 == 0 ? NR : LCM0 * NR / 2);
+    static_assert(!SRC || (LCM % NR == 0 && LCM % LCM0 == 0), "the unrolled loop covers both rings");
     const int p0 = za - K;
     VT vin[NS][RY];                 // slot (q - p0) % NS holds in(q)
     VT H[K > 1 ? K - 1 : 1][2][RY]; // H[s-1][(q - p0) & 1] holds t_s(q), s < K (HL: s >= 2 only)
+    VT vr[SRC ? NR : 1][RY];        // SRC: slot (q - p0) % NR holds rhs(q)
     // t_s(q) of parity `par`, row k: stage 1 from LDS with HL, else registers
     auto hget = [&](int s, int par, int k) -> VT {
         if (HL && s == 1) return *reinterpret_cast<const VT*>(&HLs[par][vw * RY + k][xl]);
@@ -566,6 +602,10 @@ __global__ void __launch_bounds__(64 * NW)
     }
 #pragma unroll
     for (int i = 0; i < NS - 2; ++i) load_plane(vin[i], p0 + i);
+    if constexpr (SRC) {  // rhs(p0-K) .. rhs(p0-K+NR-1)
+#pragma unroll
+        for (int i = 0; i < NR; ++i) load_rhs(vr[(i - K + NR) % NR], p0 - K + i);
+    }
     if constexpr (PROD) {  // the bottom z-ghost plane (p0 clamps to -1) into slot R
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         tier_store_plane(vin[0], tier.rmask + 1);
@@ -658,6 +698,7 @@ __global__ void __launch_bounds__(64 * NW)
                     sum += REV ? zp : zm;
                     sum += REV ? zm : zp;
                     o = DIAG == 2 ? c : __builtin_elementwise_fma(sum, (VT)(avg), VT{});
+                    if constexpr (SRC) o += vr[(S - s + 2 * NR) % NR][k];  // the second rounding
 #pragma unroll
                     for (int j = 0; j < V; ++j) {
                         if (s < K && !FAST) o[j] = (zin[s - 1] && yin[k] && xin[j]) ? o[j] : c[j];
@@ -674,6 +715,7 @@ __global__ void __launch_bounds__(64 * NW)
                     sum += REV ? zp[j] : zm[j];
                     sum += REV ? zm[j] : zp[j];
                     o[j] = DIAG == 2 ? c[j] : sfma0(sum, avg);
+                    if constexpr (SRC) o[j] += vr[(S - s + 2 * NR) % NR][k][j];  // the second rounding
                     if (s < K && !FAST) o[j] = (zin[s - 1] && yin[k] && xin[j]) ? o[j] : c[j];
                     // TIER producer: t_K keeps the ghost cells too (they go to the slots)
                     if (PROD && s == K && !FAST) o[j] = (yin[k] && xin[j]) ? o[j] : c[j];
@@ -790,6 +832,7 @@ __global__ void __launch_bounds__(64 * NW)
             if (tnb >= 0) tier_pv = tier_poll(tier_flags + tnb * kTierFlagStride);
         }
         if constexpr (DIAG != 1) load_plane(vin[(S + NS - 2) % NS], p + NS - 2);  // slot of in(p-2), consumed above
+        if constexpr (SRC) load_rhs(vr[(S - K + 2 * NR) % NR], p - K + NR);  // slot of rhs(p-K), consumed above
     };
     auto step = [&](auto S_, int p) {
         if constexpr (SFAST) {
@@ -897,20 +940,21 @@ enum : unsigned {
     kHistLds = 8,   // HL: stage 1's history in LDS
     kSplit = 16,    // SPLIT: two strips per wave
     kUmax = 32,     // UMAX: the launch reports its update maximum
+    kSrc = 64,      // SRC: every sweep adds the source grid (StripExtras::src)
 };
 template <typename T_, int V_, int RY_, int NW_, int K_, unsigned OPT = 0, int NS_ = 4, int DIAG_ = 0>
 struct Shape {
     using T = T_;
     static constexpr int V = V_, RY = RY_, NW = NW_, K = K_, NS = NS_, DIAG = DIAG_;
     static constexpr bool DB = !(OPT & kOneBuf), SIG = OPT & kSig, FP = !(OPT & kNoFast), HL = OPT & kHistLds,
-                          SPLIT = OPT & kSplit, UMAX = OPT & kUmax;
+                          SPLIT = OPT & kSplit, UMAX = OPT & kUmax, SRC = OPT & kSrc;
     using Tile = StripTile<T, V, RY, NW, K, DB, SPLIT>;
 };
 // The one place that maps a shape onto the kernel's positional parameters.
 template <class S, bool TIER = false>
 auto strip_kernel() {
     return tkstrip_7pt<typename S::T, S::V, S::RY, S::NW, S::K, S::DB, S::DIAG, S::SIG, S::NS, S::FP, S::HL, TIER,
-                       S::SPLIT, S::UMAX>;
+                       S::SPLIT, S::UMAX, S::SRC>;
 }
 
 // The default shapes (8 waves each): cells per lane and rows per strip by
@@ -945,6 +989,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     static_assert(Tl::lds_bytes + (HL ? size_t(2) * Tl::RH * Tl::RW * sizeof(T) : 0) <= 160 * 1024, "LDS budget");
     const Geom g = geom_of(l);
     const int64_t nz = end - begin;
+    if (S::SRC && !x.src) return set_error(STENCIL_EINVAL, "a source launch needs its source grid");
     if (nz <= 0 || g.nx <= 0 || g.ny <= 0) return STENCIL_OK;
     if ((g.plane + g.row + 64) * int64_t(sizeof(T)) >= (int64_t(1) << 32) || g.nz + 2 * K >= (int64_t(1) << 30))
         return set_error(STENCIL_EINVAL, "plane too large for tkstrip (4 GiB per plane, 2^30 planes)");
@@ -1096,7 +1141,8 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
         hipLaunchKernelGGL(kern, dim3(unsigned(n)), dim3(64, NW, 1), 0, s,
                            static_cast<const T*>(in), static_cast<T*>(out), g, int(begin), int(end), zc, int(gx),
                            int(gy), int(lo), int(hi), avg_weight<T>(l.prob), SIG ? x.sig : nullptr, fsig,
-                           packed ? sched : nullptr, fast_of(packed), packed ? 0 : xcd_pw, TierArgs{}, gate);
+                           packed ? sched : nullptr, fast_of(packed), packed ? 0 : xcd_pw, TierArgs{}, gate,
+                           S::SRC ? static_cast<const T*>(x.src) : nullptr);
         return hipGetLastError();
     };
     if (sched && verdict && verdict->load() == kPackUntested) return pick_schedule(verdict, s, launch);
@@ -1106,7 +1152,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
 }
 
 // ---- the two-tier launch (TIER, above): host side --------------------------
-#ifndef STRIP_ILP_TU
+#ifndef STRIP_EXTRA_TU
 using TierShape = Shape<double, 1, 7, 8, 4, kNoFast | kHistLds>;  // launched with TIER
 using TierKernelShape = TierShape::Tile;
 constexpr int kTierSlots = 16;  // R: plane slots of the producer -> consumer ring (2.2 MB each at 512^2 fp64)
@@ -1120,7 +1166,7 @@ int tier_tiles(const stencil_layout& l, int64_t* tiles) {
 
 }  // namespace
 
-#ifndef STRIP_ILP_TU
+#ifndef STRIP_EXTRA_TU
 // Can the grid run the two-tier launch?  The fp64 7-point star, K = 4 strip
 // shape, a single grid (no slab halos), at least 2K planes, and both tiers'
 // workgroups resident at once (2 x tiles <= the device's workgroup slots).
@@ -1210,7 +1256,8 @@ int tier_launch(const stencil_layout& l, const void* in, void* out, TierJob* j, 
     const int fast = 1;  // few tiles: the interior fast path pays (as the packed regime)
     hipLaunchKernelGGL(kern, dim3(unsigned(2 * j->tiles)), dim3(64, 8, 1), 0, s, static_cast<const double*>(in),
                        static_cast<double*>(out), g, 0, int(g.nz), 0, int(gx), int(gy), 0, 0,
-                       avg_weight<double>(l.prob), nullptr, nullptr, nullptr, fast, 0, j->a, StripGate{});
+                       avg_weight<double>(l.prob), nullptr, nullptr, nullptr, fast, 0, j->a, StripGate{},
+                       static_cast<const double*>(nullptr));
     STENCIL_LAUNCH_CHECK();
     j->a.base += uint32_t(g.nz + 1);  // the flags end at base + nz + 1: the next launch's origin
     return STENCIL_OK;
@@ -1235,7 +1282,7 @@ int tier_end(TierJob* j, hipStream_t s, bool* failed) {
     *failed = f != 0;
     return STENCIL_OK;
 }
-#endif  // !STRIP_ILP_TU
+#endif  // !STRIP_EXTRA_TU
 
 #ifdef STRIP_ILP_TU
 // kernels_strip_ilp.hip: the two default shapes measured faster when this file is compiled under LLVM's
@@ -1259,6 +1306,39 @@ int STRIP_ILP_FN(const stencil_layout& l, const void* in, void* out, int64_t beg
     if (l.prob.dtype == STENCIL_F32 && steps == 5)
         return launch_st<DefaultShape<float, 5, 0, TK_ILP_NS32>>(l, in, out, begin, end, s);
     return set_error(STENCIL_EINVAL, "no max-ILP strip shape for %d steps", steps);
+}
+#elif defined(STRIP_SOURCE_TU)
+// kernels_strip_source.hip: the source launches (SRC above the kernel).  The source ring
+// takes (K + 1 or K + 2) x RY lane vectors beside the input ring's 4 x RY and the histories' 2 (K - 1) x RY,
+// so the shapes take fewer rows per strip than the plain ones: K = 4 with 5-row strips (K = 3 and 2 for a
+// job's remainder), 8 waves, one fp64 / two fp32 cells per lane.  Rows per strip by [K - 2]: K = 4 with 5
+// rows takes 245 (fp32) / 256 (fp64) VGPRs and 64 KiB of LDS, no scratch (4 rows: 196 / 203, 24-row tiles
+// instead of 32); K = 3 with 6 rows 231 / 228 and 48 KiB -- 7 rows spill (44 / 48 B of scratch per lane);
+// K = 2 with 7 rows 211 / 222 and 32 KiB.  K = 4 measured 27-47 % faster than K = 3 as the job's launch
+// (DESIGN.md §5.7 has the tables).  No shape may use scratch.
+constexpr int kSourceRows[3] = {7, 6, 5};
+template <typename T, int K>
+using SourceShape = Shape<T, sizeof(T) == 8 ? 1 : 2, kSourceRows[K - 2], 8, K, kSrc>;
+
+int launch_tkstrip_source(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                          int64_t end, int steps, hipStream_t s) {
+    if (!temporal2_supports(l.prob) || (l.prob.flags & (STENCIL_HALO_LO | STENCIL_HALO_HI)))
+        return set_error(STENCIL_EUNSUPPORTED, "source sweeps cover the 3D r=1 naive 7-point star without halo flags");
+    StripExtras x;
+    x.src = src;
+    const bool f32 = l.prob.dtype == STENCIL_F32;
+    switch (steps) {
+    case 2:
+        return f32 ? launch_st<SourceShape<float, 2>>(l, in, out, begin, end, s, x)
+                   : launch_st<SourceShape<double, 2>>(l, in, out, begin, end, s, x);
+    case 3:
+        return f32 ? launch_st<SourceShape<float, 3>>(l, in, out, begin, end, s, x)
+                   : launch_st<SourceShape<double, 3>>(l, in, out, begin, end, s, x);
+    case 4:
+        return f32 ? launch_st<SourceShape<float, 4>>(l, in, out, begin, end, s, x)
+                   : launch_st<SourceShape<double, 4>>(l, in, out, begin, end, s, x);
+    default: return set_error(STENCIL_EINVAL, "fused source sweeps: steps must be 2..4 (got %d)", steps);
+    }
 }
 #else
 // Makespan (in plane steps) of workgroups of the given plane counts on
@@ -1720,11 +1800,11 @@ int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, i
                 : launch_default<kSig>(l, in, out, begin, end, steps, s, x, what);
 }
 
-#endif  // STRIP_ILP_TU
+#endif  // STRIP_ILP_TU / STRIP_SOURCE_TU
 
 }  // namespace stencil
 
-#ifndef STRIP_ILP_TU
+#ifndef STRIP_EXTRA_TU
 // The packed-schedule model on the host, without a GPU (tests, tools): see
 // include/stencil_hip.h.
 int stencil_pack_plan(int64_t tiles, int64_t planes, int32_t fill, int32_t slots, int32_t zchunk, int64_t* equal_steps,
@@ -1761,4 +1841,4 @@ int stencil_pack_table(int64_t tiles, int64_t tiles_x, int64_t planes, int32_t f
     clear_error();
     return STENCIL_OK;
 }
-#endif  // STRIP_ILP_TU
+#endif  // STRIP_EXTRA_TU

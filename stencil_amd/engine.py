@@ -384,6 +384,77 @@ class JacobiEngine:
         return UntilResult(self.b if fin.value else self.a, int(done.value), bool(conv.value), float(last.value),
                            ms.value if timed else None)
 
+    # ---------------------------------------------------------- source term
+    # u' = S(u) + g (stencil_*_source: the 3D 7-point star, r = 1, naive order).  The source grid has the
+    # field's layout; only its interior cells have meaning.
+    source: torch.Tensor | None = None
+
+    def set_source(self, dense) -> None:
+        """The source term g of iterate_source / iterate_until_source, already
+        scaled by the caller: a dense (nz, ny, nx) array or tensor, or the
+        ghost-padded oracle shape (its ghost cells are ignored).  Allocates the
+        source grid on first use (zero outside the interior); None drops it."""
+        if dense is None:
+            self.source = None
+            return
+        p, r = self.prob, self.r
+        inner = (p.nz, p.ny, p.nx)
+        padded = (p.nz + 2 * r, p.ny + 2 * r, p.nx + 2 * r)
+        t = torch.as_tensor(dense)
+        if tuple(t.shape) == padded and padded != inner:
+            t = t[r:-r, r:-r, r:-r]
+        elif tuple(t.shape) != inner:
+            raise ValueError(f"source of shape {tuple(t.shape)}: expected {inner} or {padded}")
+        if self.source is None:
+            self.source = torch.zeros(int(self.layout.elems) + 256 // self.spec.elem_bytes, dtype=self.torch_dtype,
+                                      device=self.device)
+        self.interior(self.source).copy_(t.to(device=self.device, dtype=self.torch_dtype))
+
+    def _source_ptr(self) -> ctypes.c_void_p:
+        if self.source is None:
+            raise ValueError("no source term: call set_source() first")
+        return ctypes.c_void_p(self.source.data_ptr())
+
+    def sweepk_source(self, src_grid: torch.Tensor, dst_grid: torch.Tensor, begin: int, end: int, steps: int,
+                      stream=None) -> None:
+        """dst = `steps` source sweeps of src over [begin, end) in one launch
+        (stencil_sweepk_source; steps 1..4), the source being set_source()'s."""
+        _lib.check(self.lib.stencil_sweepk_source(ctypes.byref(self.layout), ctypes.c_void_p(src_grid.data_ptr()),
+                                                  ctypes.c_void_p(dst_grid.data_ptr()), self._source_ptr(), begin, end,
+                                                  steps, _stream_handle(stream)), "stencil_sweepk_source", lib=self.lib)
+
+    def iterate_source(self, iterations: int, stream=None, timed: bool = False):
+        """iterate() with the source added after every sweep
+        (stencil_iterate_source); returns (final grid tensor, device ms or None)."""
+        fin, ms = ctypes.c_int(0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_iterate_source(ctypes.byref(self.layout), ctypes.c_void_p(self.a.data_ptr()),
+                                                   ctypes.c_void_p(self.b.data_ptr()), self._source_ptr(), iterations,
+                                                   _stream_handle(stream), ctypes.byref(fin),
+                                                   ctypes.byref(ms) if timed else None),
+                   "stencil_iterate_source", lib=self.lib)
+        return (self.b if fin.value else self.a), (ms.value if timed else None)
+
+    def iterate_until_source(self, tol: float, max_iterations: int, check_every: int = 100, norm: str = "max",
+                             stream=None, timed: bool = False) -> "UntilResult":
+        """iterate_until() on source sweeps (stencil_iterate_until_source)."""
+        done, fin, conv = ctypes.c_uint32(0), ctypes.c_int(0), ctypes.c_int(0)
+        last, ms = ctypes.c_double(0.0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_iterate_until_source(
+            ctypes.byref(self.layout), ctypes.c_void_p(self.a.data_ptr()), ctypes.c_void_p(self.b.data_ptr()),
+            self._source_ptr(), max_iterations, check_every, _lib.NORM_NAMES[norm], tol, _stream_handle(stream),
+            ctypes.byref(done), ctypes.byref(fin), ctypes.byref(last), ctypes.byref(conv),
+            ctypes.byref(ms) if timed else None), "stencil_iterate_until_source", lib=self.lib)
+        return UntilResult(self.b if fin.value else self.a, int(done.value), bool(conv.value), float(last.value),
+                           ms.value if timed else None)
+
+    def source_plan(self, iterations: int) -> dict:
+        """iterate_source(iterations) as kernel launches, and the sweeps its
+        fused launch takes (stencil_source_plan, host only)."""
+        launches, steps = ctypes.c_int64(0), ctypes.c_int32(0)
+        _lib.check(self.lib.stencil_source_plan(ctypes.byref(self.layout), iterations, ctypes.byref(launches),
+                                                ctypes.byref(steps)), "stencil_source_plan", lib=self.lib)
+        return {"launches": int(launches.value), "steps": int(steps.value)}
+
 
 @dataclass(frozen=True)
 class UntilResult:
