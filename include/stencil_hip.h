@@ -393,6 +393,23 @@ int stencil_pack_plan(int64_t tiles, int64_t planes, int32_t fill, int32_t slots
  * *workgroups (0: no packed grid). */
 int stencil_pack_table(int64_t tiles, int64_t tiles_x, int64_t planes, int32_t fill, int32_t slots, int32_t zchunk,
                        int32_t xcd_width, int32_t* table, int64_t capacity, int64_t* workgroups);
+/* The packed grid of the fp64 K = 4 strip's sliver mode (host only), where the
+ * last tile column -- at most 8 columns wide -- runs as sliver workgroups of
+ * four tile rows each: for an nx x ny plane of `planes` planes on `slots`
+ * workgroup slots, geometry[0..3] = tile columns, tile rows, main (full-width)
+ * tiles and schedule tiles (main + sliver workgroups; both 0 where the mode is
+ * off: one tile column, a last column wider than 8, more than 2 tiles per
+ * slot, more schedule tiles than slots).  The mode runs only with this table:
+ * where it is empty (fewer than 8 planes) the launch is the plain tile grid's.  The table is stencil_pack_table's for that tile count: tile < main
+ * is main tile (tile % (columns - 1), tile / (columns - 1)), tile >= main
+ * sliver workgroup tile - main (tile rows 4j .. 4j + 3 of the last column).
+ * The main tiles take chunks of Lc planes, the sliver workgroups of
+ * ceil(Lc / 2) (they take longer per plane); Lc is the model's best among the
+ * tables whose full chunks fit the slots at once, or chunk_planes when that is
+ * > 0 (as STENCIL_TK_PACK_LC).  xcd_width as stencil_pack_table's, the patches
+ * over the main tiles. */
+int stencil_sliver_table(int64_t nx, int64_t ny, int64_t planes, int32_t slots, int32_t chunk_planes,
+                         int32_t xcd_width, int64_t* geometry, int32_t* table, int64_t capacity, int64_t* workgroups);
 
 /* Launch plan of stencil_iterate for `iterations`: number of kernel launches
  * and the kernel family AUTO resolves to. */

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "stencil_sweepk_signal_update_max", "stencil_sweepk_signal_update_max_gated",
     "stencil_slab_run_until", "stencil_slab_until_plan",
     "stencil_sweepk_source", "stencil_iterate_source", "stencil_source_plan", "stencil_iterate_until_source",
+    "stencil_sliver_table",
 )
 
 
@@ -166,6 +167,8 @@ def signatures() -> dict:
                                       POINTER(c_int64), POINTER(c_int64)]),
         "stencil_pack_table": (c_int, [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32),
                                        c_int64, POINTER(c_int64)]),
+        "stencil_sliver_table": (c_int, [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int64),
+                                         POINTER(c_int32), c_int64, POINTER(c_int64)]),
         "stencil_plan": (c_int, [L, c_uint32, POINTER(c_int64), POINTER(c_int32)]),
         "stencil_plane_sums": (c_int, [L, c_void_p, POINTER(c_double), c_void_p]),
         "stencil_copy_bandwidth": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, POINTER(c_float)]),

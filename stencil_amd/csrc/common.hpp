@@ -127,9 +127,16 @@ extern const int* const kDrySchedule;
 // strips of xcd_w tiles cut into 8 runs -- and neighbouring tiles' shared
 // halo lines become hits in that XCD's L2 (xcd_patch_order).  Same lengths
 // at the same positions: the same makespan.
+// main_tiles > 0 (the 7-point strip's sliver mode): only tiles [0, main_tiles)
+// form the tiles_x-wide grid the patches order; the tiles after them (sliver
+// workgroups) stay behind the main tiles of their generation.  Part of the
+// cache key: the two modes of one kernel keep separate tables and verdicts.
+// Such a table comes from the mode's own search (sliver_pack_search), stands
+// without the 2 % rule, and its trial's other side is the plain-grid launch:
+// its verdict kPackEqual means "the plain launch" (launch_st).
 int packed_schedule(const void* kern, int dev, int64_t tiles, int64_t nz, int K, int fill, int slots, int zc,
                     hipStream_t s, bool dry, const int** sched, int64_t* nb, std::atomic<int>** verdict = nullptr,
-                    bool faces_out = false, int64_t tiles_x = 0, int xcd_w = 0);
+                    bool faces_out = false, int64_t tiles_x = 0, int xcd_w = 0, int64_t main_tiles = 0);
 
 // The dispatcher model behind packed_schedule mispredicts some shapes badly
 // (measured: 504 x 512 x 512 fp64 packed 0.555 vs equal 0.450 ms per launch,

@@ -123,6 +123,18 @@ constexpr int kSShr1 = 0x138, kSShl1 = 0x130;  // wave_shr:1 / wave_shl:1
 // per-step choice (kFast shapes), kFastSeg = the per-segment choice
 // (TK_SEG_FAST), kFastAll = every tile taken as inside (timing only: wrong ghost cells)
 constexpr int kFastStep = 1, kFastAll = 2, kFastSeg = 4;
+// kSliver (launch_st sets it, never the knob): the launch is in sliver mode (SLIVER above the kernel)
+constexpr int kSliver = 8;
+// The one shape that compiles the sliver segment: the plain default fp64 K = 4 strip (this file's
+// instance and the max-ILP build's).  Every other shape compiles to what it compiled to without it.
+template <typename T, int V, int RY, int NW, int K, bool DB, int DIAG, bool SIG, int NS, bool FP, bool HL, bool TIER,
+          bool SPLIT, bool UMAX, bool SRC>
+constexpr bool sliver_shape() {
+    return sizeof(T) == 8 && V == 1 && RY == 7 && NW == 8 && K == 4 && DB && DIAG == 0 && !SIG && NS == 4 && FP && !HL &&
+           !TIER && !SPLIT && !UMAX && !SRC && !TK_PROBE_NOBAR;
+}
+// lanes of a region row that one ragged-column tile of a sliver workgroup takes, and tiles per workgroup
+constexpr int kSliverLanes = 16, kSliverRows = 4;
 
 // The plane loop unrolled N steps (compile-time step index), and the tail of
 // fewer than N steps.
@@ -300,6 +312,17 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // is dropped by the ghost-cell selects (s < K) or never stored (s = K), and the
 // select-free segments compute such cells only in planes that never reach the
 // output.
+// SLIVER (sliver_shape() only; fast & kSliver): the last tile column stores at most
+// 16 - 2 XR = 8 columns, so one of its tiles needs 16 lanes of a region row: XR ring lanes, its
+// output columns, the ghost column x = nx, the rest unused.  A SLIVER WORKGROUP runs four such tiles
+// side by side, tile rows by = 4j .. 4j+3 of that column, one per 16-lane group: lane l works for
+// tile row 4j + (l >> 4) at x = bx TX - XR + (l & 15).  Everything in z stays uniform (chunk, plane
+// step, zin, do_store, plane bases); what depends on the tile row -- y0, off[k], yin[k], st[k] -- is
+// per lane.  The boundary rows in LDS are indexed by lane, so each group has its own 16 columns; the
+// x lane shifts cross a group boundary only into the neighbour group's ring lanes, which never reach
+// a stored cell.  A group whose tile row does not exist clamps its row and stores nothing.  Tile
+// indices: [0, main_tiles) are the (tiles_x - 1) x tiles_y full-width tiles, row-major;
+// main_tiles + j is sliver workgroup j.
 template <typename T, int V, int RY, int NW, int K, bool DB, int DIAG = 0, bool SIG = false, int NS = 4, bool FP = true,
           bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false, bool SRC = false>
 __global__ void __launch_bounds__(64 * NW)
@@ -334,7 +357,21 @@ __global__ void __launch_bounds__(64 * NW)
     // per slot), walked as one segment per tile it touches -- no partial last
     // round, at the price of one extra pipeline fill per segment boundary.
     const int nzr = zend - zbeg;
-    const int64_t tiles = int64_t(tiles_x) * tiles_y;
+    // Tile index -> position, for every work split below: main tile t is column t % mx, row t / mx;
+    // in sliver mode the last column's tiles follow as sliver workgroups of kSliverRows tile rows each
+    constexpr bool SLVC = sliver_shape<T, V, RY, NW, K, DB, DIAG, SIG, NS, FP, HL, TIER, SPLIT, UMAX, SRC>();
+    // (`if constexpr`: the shapes without the mode keep their code to the instruction)
+    bool slv = false;
+    int mx = tiles_x;  // main tile columns
+    if constexpr (SLVC) {
+        slv = fast & kSliver;
+        if (slv) mx = tiles_x - 1;
+    }
+    const int64_t main_tiles = int64_t(mx) * tiles_y;
+    int64_t tiles = main_tiles;
+    if constexpr (SLVC) {
+        if (slv) tiles += (tiles_y + kSliverRows - 1) / kSliverRows;
+    }
     int64_t lo, hi;
     bool rev = false;  // this workgroup's chunk marches down (SIG: the last chunk)
     static_assert(!TIER || (!SIG && sizeof(T) * V == 8), "TIER: plain launches of 8-byte lane vectors");
@@ -363,9 +400,14 @@ __global__ void __launch_bounds__(64 * NW)
             if (u >= total) return;  // whole workgroup, before any barrier
             c = u / tiles;
             const int64_t tt = u - c * tiles;
-            const int64_t strip = tt / (int64_t(xcd_pw) * tiles_y), rem = tt - strip * xcd_pw * tiles_y;
-            const int64_t sw = tiles_x - strip * xcd_pw < xcd_pw ? tiles_x - strip * xcd_pw : xcd_pw;
-            t = rem / sw * tiles_x + strip * xcd_pw + rem % sw;
+            // (the main tiles only: a sliver workgroup keeps its place behind their patches)
+            const int64_t tm = SLVC && tt >= main_tiles ? 0 : tt;
+            const int64_t strip = tm / (int64_t(xcd_pw) * tiles_y), rem = tm - strip * xcd_pw * tiles_y;
+            const int64_t sw = mx - strip * xcd_pw < xcd_pw ? mx - strip * xcd_pw : xcd_pw;
+            t = rem / sw * mx + strip * xcd_pw + rem % sw;
+            if constexpr (SLVC) {
+                if (tt >= main_tiles) t = tt;
+            }
         }
         const int64_t nch = (nzr + zchunk - 1) / zchunk;
         // face-signalled launches of several chunks per tile: the two face
@@ -426,25 +468,43 @@ __global__ void __launch_bounds__(64 * NW)
         const int t = int(lo / nzr);
         const int za = zbeg + int(lo - int64_t(t) * nzr);
         const int zb = za + (hi - lo < int64_t(zend - za) ? int(hi - lo) : zend - za);
-        if (!region_inner(t % tiles_x, t / tiles_x, 1)) return false;
+        if constexpr (SLVC) {
+            if (t >= main_tiles) return false;  // a sliver segment: its regions hold the ghost column
+        }
+        if (!region_inner(t % mx, t / mx, 1)) return false;
         // strongest at s = 1 (the widest reach): [za - K + 1, zb + K - 1)
         return za - (K - 1) >= (halo_lo ? -(K - 1) : 0) && zb + K - 1 <= (halo_hi ? nz + K - 1 : nz);
     };
     // UMAX: this lane's max |t_K - t_{K-1}| over the cells it has stored, and whether one was NaN
     double umax = 0.0;
     bool unan = false;
-    auto segment = [&](auto REV_, auto PROD_, auto SFAST_) {  // one segment: tile t, planes [za, zb)
+    auto segment = [&](auto REV_, auto PROD_, auto SFAST_, auto SLIV_) {  // one segment: tile t, planes [za, zb)
     constexpr bool REV = decltype(REV_)::value;
     constexpr bool SFAST = decltype(SFAST_)::value;  // the whole segment without ghost-cell selects
+    constexpr bool SLIV = SLVC && decltype(SLIV_)::value;  // a sliver workgroup's segment (never SFAST)
+    static_assert(!SLIV || (!SFAST && !REV && LW == 64 && V == 1 && kSliverLanes >= 2 * XR + 2),
+                  "a sliver tile: its ring, an output column and the ghost column in one lane group");
     constexpr bool PROD = TIER && decltype(PROD_)::value;  // TIER producer (stores t_K into the slots)
     constexpr bool CONS = TIER && !PROD;                   // TIER consumer (reads the slots)
     const int t = int(lo / nzr);
     const int za = zbeg + int(lo - int64_t(t) * nzr);
     const int zb = za + (hi - lo < int64_t(zend - za) ? int(hi - lo) : zend - za);
     lo += zb - za;
-    const int bx = t % tiles_x;
-    const int by = t / tiles_x;
-    const int64_t x = int64_t(bx) * TX - XR * V + int64_t(hl) * V;
+    int bx = t % mx;
+    int by = t / mx;
+    // SLIV: this lane's tile row, of the kSliverRows the workgroup holds (a row past the grid's last
+    // clamps to it and stores nothing), and its lane within the tile's kSliverLanes-wide region row
+    [[maybe_unused]] bool row_on = true;
+    int hx = hl;
+    constexpr int LWX = SLIV ? kSliverLanes : LW;
+    if constexpr (SLIV) {
+        bx = mx;
+        by = int(t - main_tiles) * kSliverRows + lane / kSliverLanes;
+        row_on = by < tiles_y;
+        by = row_on ? by : tiles_y - 1;
+        hx = lane % kSliverLanes;
+    }
+    const int64_t x = int64_t(bx) * TX - XR * V + int64_t(hx) * V;
     const int64_t y0 = int64_t(by) * TY - K + int64_t(vw) * RY;  // this strip's first row
 
     // Unconditional loads from clamped addresses (kernels_temporalk.hip): the
@@ -461,6 +521,7 @@ __global__ void __launch_bounds__(64 * NW)
         off[k] = uint32_t((yc * g.row + xc + bias) * int64_t(sizeof(T)));
         yin[k] = y >= 0 && y < g.ny;
         st[k] = rr >= K && rr < RH - K && y < g.ny && hl >= XR && hl < LW - XR;
+        if constexpr (SLIV) st[k] = rr >= K && rr < RH - K && y < g.ny && hx >= XR && hx < LWX - XR && row_on;
     }
     // SST: the 16-B store lanes (cells 4(l%32) .. +3 of strip row 2i + l/32)
     uint32_t soff[SST ? NI : 1];
@@ -509,7 +570,7 @@ __global__ void __launch_bounds__(64 * NW)
     uint32_t tier_pv = 0;  // the prefetched flag
     // the whole region inside the grid in x and y: intermediate stages need no
     // ghost-cell select on steps whose stage planes are all inside in z
-    const bool xy_inner = region_inner(bx, by, fast & kFastStep);
+    const bool xy_inner = !SLIV && region_inner(bx, by, fast & kFastStep);
     const int ld_lo = halo_lo ? -K : -1;
     const int ld_hi = halo_hi ? nz + K - 1 : nz;
     const int zfirst = za - K > ld_lo ? za - K : ld_lo;
@@ -841,7 +902,8 @@ __global__ void __launch_bounds__(64 * NW)
         }
         // compiled for the fp64 one-cell-per-lane shapes only: duplicating the
         // step costs the fp32 / signalled shapes their register fit
-        constexpr bool kFast = TK_FAST_PATH && FP && sizeof(T) == 8 && V == 1 && !SIG && DIAG == 0;
+        // (nor for a sliver segment: its regions always hold the ghost column)
+        constexpr bool kFast = TK_FAST_PATH && FP && sizeof(T) == 8 && V == 1 && !SIG && DIAG == 0 && !SLIV;
         if constexpr (!kFast) {
             stepb(S_, p, std::false_type{});
             return;
@@ -885,23 +947,29 @@ __global__ void __launch_bounds__(64 * NW)
     using F = std::false_type;
     using Tr = std::true_type;
     while (lo < hi) {
+        if constexpr (SLVC) {
+            if (slv && lo / nzr >= main_tiles) {
+                segment(F{}, F{}, F{}, Tr{});
+                continue;
+            }
+        }
         if constexpr (TIER) {
-            if (tprod) segment(F{}, Tr{}, F{});
-            else segment(F{}, F{}, F{});
+            if (tprod) segment(F{}, Tr{}, F{}, F{});
+            else segment(F{}, F{}, F{}, F{});
         } else if constexpr (kSegFast) {
             const bool sf = seg_fast();
             if (SIG && rev) {
-                if (sf) segment(Tr{}, F{}, Tr{});
-                else segment(Tr{}, F{}, F{});
+                if (sf) segment(Tr{}, F{}, Tr{}, F{});
+                else segment(Tr{}, F{}, F{}, F{});
             } else {
-                if (sf) segment(F{}, F{}, Tr{});
-                else segment(F{}, F{}, F{});
+                if (sf) segment(F{}, F{}, Tr{}, F{});
+                else segment(F{}, F{}, F{}, F{});
             }
         } else if constexpr (SIG) {
-            if (rev) segment(Tr{}, F{}, F{});
-            else segment(F{}, F{}, F{});
+            if (rev) segment(Tr{}, F{}, F{}, F{});
+            else segment(F{}, F{}, F{}, F{});
         } else {
-            segment(F{}, F{}, F{});
+            segment(F{}, F{}, F{}, F{});
         }
     }
     if constexpr (UMAX) {
@@ -979,6 +1047,38 @@ constexpr int default_rows() {
 template <typename T, int K, unsigned OPT = 0, int NS = 4>
 using DefaultShape = Shape<T, kDefaultStrip[sizeof(T) == 8][K - 3].v, default_rows<T, K, OPT>(), 8, K, OPT, NS>;
 
+// Whole z-chunks: the chunk count per tile minimising rounds x (chunk + 2K) on `slots` workgroup slots.
+inline int64_t whole_chunk_count(int64_t tiles, int64_t nz, int K, int slots) {
+    int64_t best_c = 1, best = INT64_MAX;
+    for (int64_t c = 1; c <= nz; ++c) {
+        const int64_t z = (nz + c - 1) / c;
+        if (c > 1 && z < 2 * K) break;
+        const int64_t cost = ((tiles * c + slots - 1) / slots) * (z + 2 * K);
+        if (cost <= best) best = cost, best_c = c;
+    }
+    return best_c;
+}
+
+// Sliver mode's geometry rule (SLIVER above the kernel) for an nx x ny plane in TX x TY tiles with `ring`
+// ring lanes per x side, on `slots` workgroup slots: at least two tile columns, the last one's columns and
+// its ghost column fit one lane group beside the ring, the grid is in the packed regime (at most 2
+// tiles per slot), and the mode's own tiles fit the slots at once -- else no packed table has its full
+// chunks resident together (pack_search), and without its table the mode is not used (launch_st).
+// *main_tiles = the full-width tiles, *tiles = those + the sliver workgroups.
+inline bool sliver_geometry(int64_t nx, int64_t ny, int TX, int TY, int ring, int slots, int64_t* main_tiles,
+                            int64_t* tiles) {
+    const int64_t gx = (nx + TX - 1) / TX, gy = (ny + TY - 1) / TY;
+    if (gx < 2 || nx - (gx - 1) * TX > kSliverLanes - 2 * ring || gx * gy > 2 * int64_t(slots)) return false;
+    const int64_t m = (gx - 1) * gy, t = m + (gy + kSliverRows - 1) / kSliverRows;
+    if (t > slots) return false;
+    *main_tiles = m;
+    *tiles = t;
+    return true;
+}
+// set while a sliver-mode launch_st runs the plain launch of the same call (its trial's other side, or
+// its fall-back): that launch_st keeps the gx x gy tile grid
+thread_local bool tl_plain_grid = false;
+
 template <class S>
 int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, hipStream_t s,
               const StripExtras& x = StripExtras{}) {
@@ -995,10 +1095,39 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
         return set_error(STENCIL_EINVAL, "plane too large for tkstrip (4 GiB per plane, 2^30 planes)");
     const int64_t gx = (g.nx + Tl::TX - 1) / Tl::TX, gy = (g.ny + Tl::TY - 1) / Tl::TY;
     auto kern = strip_kernel<S>();
-    const int64_t tiles = gx * gy;
     int dev = 0, slots = 0;
     STENCIL_HIP_CHECK(hipGetDevice(&dev));
     if (const int rc = resident_slots(kern, 64 * NW, &slots)) return rc;
+    // Sliver mode (SLIVER above the kernel): the plain launch of the sliver shape -- no halo flags, no
+    // extras -- where sliver_geometry() holds, in the calls of >= kSustainedSweeps sweeps: there it
+    // measured +2.5 % at 512^3 (1252 vs 1222 Gcell/s over 1000 sweeps), while the 20-sweep call, below
+    // the power limit, ran 1 % slower (1216 vs 1229, eight alternating runs each; profiles/r07).
+    // The mode stands on its packed table (half-length sliver chunks, pack_search): with equal chunks it
+    // measured 7-8 % slower than the plain gx x gy grid.  So where no table is in use -- none exists,
+    // STENCIL_TK_PACK=0, a capturing stream before the upload, or the trial's verdict -- the call runs
+    // the plain launch (plain_launch below), and the first launch's trial times the sliver table against
+    // that plain launch, not against sliver equal chunks: a shape where the mode does not pay keeps
+    // the launch it had.
+    // STENCIL_TK_SLIVER (debug library): 0 = never; 1 = every qualifying launch, whatever its schedule
+    // and untimed (the tests' forced equal chunks and tables).
+    int64_t tiles = gx * gy, main_tiles = 0;
+    bool sliver = false, sliver_forced = false;
+    if constexpr (sliver_shape<T, V, RY, NW, K, S::DB, S::DIAG, SIG, S::NS, S::FP, HL, false, S::SPLIT, S::UMAX,
+                               S::SRC>()) {
+        const bool plain = !(l.prob.flags & (STENCIL_HALO_LO | STENCIL_HALO_HI)) && !x.signal && !x.sig && !x.fsig &&
+                           !x.umax && !x.gate.word && !x.nsig && !x.src;
+        const int want = senv_int("STENCIL_TK_SLIVER", -1);
+        sliver_forced = want > 0;
+        sliver = plain && !tl_plain_grid && (want > 0 || (want < 0 && tl_sustained)) &&
+                 sliver_geometry(g.nx, g.ny, Tl::TX, Tl::TY, Tl::XR * V, slots, &main_tiles, &tiles);
+    }
+    // the same call on the plain tile grid (with that grid's own table, trial and verdict)
+    auto plain_launch = [&]() -> int {
+        tl_plain_grid = true;
+        const int rc = launch_st<S>(l, in, out, begin, end, s, x);
+        tl_plain_grid = false;
+        return rc;
+    };
     int zc = senv_int("STENCIL_TK_ZCHUNK", 0);
     int64_t nb = 0;
     if (zc > 0) {
@@ -1017,13 +1146,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
             zc = 0;  // one equal share per workgroup (the kernel's zchunk == 0 mode); never packed
         } else {
             // whole chunks: the count minimising rounds x (chunk + 2K)
-            int64_t best_c = 1, best = INT64_MAX;
-            for (int64_t c = 1; c <= nz; ++c) {
-                const int64_t z = (nz + c - 1) / c;
-                if (c > 1 && z < 2 * K) break;
-                const int64_t cost = ((tiles * c + slots - 1) / slots) * (z + 2 * K);
-                if (cost <= best) best = cost, best_c = c;
-            }
+            int64_t best_c = whole_chunk_count(tiles, nz, K, slots);
             // A slab of a multi-GPU job (halo flags): its halo exchange runs
             // kernels (RCCL P2P, or the face wait) beside this launch, and a
             // grid that fills every CU for several rounds loses a whole round
@@ -1086,12 +1209,16 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
         // below it: DESIGN.md §5.1), tile-major otherwise; STENCIL_TK_PACK_XCD
         // (debug library): that width always (0: tile-major)
         const int pack_xcd = senv_int("STENCIL_TK_PACK_XCD", tl_sustained ? -1 : 0);
-        const int rc = packed_schedule(reinterpret_cast<const void*>(kern), dev, gx * gy, nz, K, 2 * K, pslots, zc, s,
-                                       tl_dry_launch != nullptr, &sched, &nb, &verdict, SIG, gx, pack_xcd);
+        // (sliver mode: the patches order the main tiles, gx - 1 columns; the sliver entries follow them)
+        const int rc = packed_schedule(reinterpret_cast<const void*>(kern), dev, tiles, nz, K, 2 * K, pslots, zc, s,
+                                       tl_dry_launch != nullptr, &sched, &nb, &verdict, SIG, sliver ? gx - 1 : gx,
+                                       pack_xcd, main_tiles);
         if (rc != STENCIL_OK) return rc;
-        if (pack_mode != 1 || SIG) verdict = nullptr;  // 2: the model's choice, unmeasured
+        if (pack_mode != 1 || SIG || sliver_forced) verdict = nullptr;  // 2: the model's choice, unmeasured
         if (verdict && verdict->load() == kPackEqual) sched = nullptr, nb = nb_equal, verdict = nullptr;
     }
+    // sliver mode without its table in use (a sliver table's verdict kPackEqual: the plain launch won)
+    if (sliver && !sliver_forced && !sched) return plain_launch();
     if (nb > (int64_t(1) << 31) - 1) return set_error(STENCIL_EINVAL, "grid too large for tkstrip");
     // interior steps without ghost-cell selects, per step (fp64 one-cell-per-lane
     // shapes): by default only where the packed schedule runs -- few tiles,
@@ -1099,12 +1226,17 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     // step loses (2048^2 x 512 1357 vs 1384, 2048^3 1310 vs 1365;
     // profiles/r02o_ab_tk_fast.log); per segment (TK_SEG_FAST) wherever compiled
     const int fast_env = senv_int("STENCIL_TK_FAST", -1);
-    auto fast_of = [&](bool packed) { return fast_env >= 0 ? fast_env : (packed ? kFastStep : 0) | kFastSeg; };
+    auto fast_of = [&](bool packed) {
+        return (fast_env >= 0 ? fast_env & (kSliver - 1) : (packed ? kFastStep : 0) | kFastSeg) | (sliver ? kSliver : 0);
+    };
     if (senv_int("STENCIL_TK_VERBOSE", 0)) {
         int per_cu = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * NW, 0);
         std::fprintf(stderr, "tkstrip K=%d V=%d RY=%d NW=%d: tiles %lldx%lld, zchunk %d, %lld workgroups, %d per CU\n", K,
                      V, RY, NW, (long long)gx, (long long)gy, zc, (long long)nb, per_cu);
+        if (sliver)
+            std::fprintf(stderr, "tkstrip sliver mode: %lld main tiles + %lld sliver workgroups per chunk\n",
+                         (long long)main_tiles, (long long)(tiles - main_tiles));
     }
     const bool lo = l.prob.flags & STENCIL_HALO_LO, hi = l.prob.flags & STENCIL_HALO_HI;
     if ((lo || hi) && l.zghost < K)
@@ -1137,6 +1269,9 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     unsigned long long* fsig = SIG ? x.fsig : nullptr;
     if (S::UMAX) (SIG ? gate.umax : fsig) = x.umax;
     auto launch = [&](bool packed) {
+        // the sliver table's trial: its other side is the plain launch (whose own first call settles its
+        // own trial inside; pick_schedule keeps each side's best of three)
+        if (!packed && sliver && !sliver_forced) return plain_launch() == STENCIL_OK ? hipSuccess : hipErrorUnknown;
         const int64_t n = packed ? nb : (xcd_pw > 0 ? (nb_equal + 7) / 8 * 8 : nb_equal);
         hipLaunchKernelGGL(kern, dim3(unsigned(n)), dim3(64, NW, 1), 0, s,
                            static_cast<const T*>(in), static_cast<T*>(out), g, int(begin), int(end), zc, int(gx),
@@ -1360,6 +1495,32 @@ static int64_t simulate_makespan(const std::vector<int>& len, int fill, int slot
     return span;
 }
 
+// One packed table: chunks of lc planes per tile (the last one shorter), of
+// ceil(lc / sliver_div) for the tiles from main_tiles on (main_tiles > 0: the
+// strip's sliver workgroups), longest first; returns its simulated makespan.
+static int64_t build_pack_table(int64_t tiles, int64_t nz, int fill, int slots, int64_t lc0, std::vector<int>& tab,
+                                int64_t main_tiles = 0, int sliver_div = 1) {
+    lc0 = std::max<int64_t>(1, lc0);
+    struct Item { int len, c, t, z; };
+    std::vector<Item> items;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int64_t lc =
+            main_tiles > 0 && t >= main_tiles ? std::max<int64_t>(1, (lc0 + sliver_div - 1) / sliver_div) : lc0;
+        for (int64_t z = 0, c = 0; z < nz; z += lc, ++c)
+            items.push_back({int(std::min<int64_t>(lc, nz - z)), int(c), int(t), int(z)});
+    }
+    std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) {
+        return a.len != b.len ? a.len > b.len : (a.c != b.c ? a.c < b.c : a.t < b.t);
+    });
+    std::vector<int> len;
+    tab.clear();
+    for (const Item& it : items) {
+        len.push_back(it.len);
+        tab.insert(tab.end(), {it.t, it.z, it.len});
+    }
+    return simulate_makespan(len, fill, slots);
+}
+
 // The dispatcher-model search behind packed_schedule (host only): chunks of
 // Lc planes per tile, longest first, for every Lc in [max(fill, nz/16), nz];
 // *base = the simulated makespan of equal chunks of zc planes, *best the best
@@ -1367,38 +1528,50 @@ static int64_t simulate_makespan(const std::vector<int>& len, int fill, int slot
 // plane, planes} table (empty when no Lc beats equal chunks).
 static void pack_search(int64_t tiles, int64_t nz, int fill, int slots, int zc, int force_lc, std::vector<int>* tab_out,
                         int64_t* base_out, int64_t* best_out) {
-    auto build = [&](int64_t lc, std::vector<int>& tab) {
-        lc = std::max<int64_t>(1, lc);
-        struct Item { int len, c, t, z; };
-        std::vector<Item> items;
-        for (int64_t t = 0; t < tiles; ++t)
-            for (int64_t z = 0, c = 0; z < nz; z += lc, ++c)
-                items.push_back({int(std::min<int64_t>(lc, nz - z)), int(c), int(t), int(z)});
-        std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) {
-            return a.len != b.len ? a.len > b.len : (a.c != b.c ? a.c < b.c : a.t < b.t);
-        });
-        std::vector<int> len;
-        tab.clear();
-        for (const Item& it : items) {
-            len.push_back(it.len);
-            tab.insert(tab.end(), {it.t, it.z, it.len});
-        }
-        return simulate_makespan(len, fill, slots);
-    };
     std::vector<int> tab, best_tab;
-    const int64_t base = build(zc, tab);
+    const int64_t base = build_pack_table(tiles, nz, fill, slots, zc, tab);
     int64_t best = base;
     for (int64_t lc = std::max<int64_t>(fill, nz / 16); lc <= nz && force_lc <= 0; lc += std::max<int64_t>(1, nz / 256)) {
-        const int64_t m = build(lc, tab);
+        const int64_t m = build_pack_table(tiles, nz, fill, slots, lc, tab);
         if (m < best) best = m, best_tab = tab;
     }
     if (force_lc > 0) {
-        build(force_lc, best_tab);
+        build_pack_table(tiles, nz, fill, slots, force_lc, best_tab);
         best = -1;  // always used
     }
     *tab_out = std::move(best_tab);
     *base_out = base;
     *best_out = best;
+}
+
+// The sliver mode's search (tiles from main_tiles on are sliver workgroups).
+// A sliver workgroup takes about 10 % longer per plane step than a full tile
+// (512^3: 1103 vs 1200 Gcell/s with equal chunk lengths, profiles/r07), so with
+// chunks as long as the main tiles' it is the launch's critical path; it takes
+// chunks of Lc / kSliverChunkDiv planes instead.  Lc is the best of the tables
+// with EQUAL lengths whose full chunks are all resident at once, in z lock-step
+// -- there the model's optimum matches the measured one, 222 planes at 512^3;
+// several rounds of near-equal chunks are what the model overrates (222 steps,
+// measured 8 % slower than the plain grid's 240).  *best = the makespan of the
+// table emitted, half-length sliver chunks included (-1 with force_lc); the
+// table is returned whether or not it beats *base, the equal chunks' makespan:
+// the first launch's trial times it against the plain launch (launch_st).
+// Empty when no Lc qualifies (more tiles than slots, fewer planes than `fill`).
+constexpr int kSliverChunkDiv = 2;
+static void sliver_pack_search(int64_t tiles, int64_t main_tiles, int64_t nz, int fill, int slots, int zc, int force_lc,
+                               std::vector<int>* tab_out, int64_t* base_out, int64_t* best_out) {
+    std::vector<int> tab, best_tab;
+    const int64_t base = build_pack_table(tiles, nz, fill, slots, zc, tab);
+    int64_t best = INT64_MAX, best_lc = force_lc;
+    for (int64_t lc = std::max<int64_t>(fill, nz / 16); lc <= nz && force_lc <= 0; lc += std::max<int64_t>(1, nz / 256)) {
+        if (tiles * (nz / lc) > slots) continue;
+        const int64_t m = build_pack_table(tiles, nz, fill, slots, lc, tab);
+        if (m < best) best = m, best_lc = lc;
+    }
+    best = best_lc > 0 ? build_pack_table(tiles, nz, fill, slots, best_lc, best_tab, main_tiles, kSliverChunkDiv) : base;
+    *tab_out = std::move(best_tab);
+    *base_out = base;
+    *best_out = force_lc > 0 ? -1 : best;
 }
 
 const int* const kDrySchedule = reinterpret_cast<const int*>(uintptr_t(16));
@@ -1449,7 +1622,9 @@ static bool faces_outward(std::vector<int>& tab, int64_t nz) {
 // Reorder a packed table's generations into XCD patches (packed_schedule's
 // xcd_w, common.hpp).  A generation is a run of entries with the same
 // length and first plane (the tiles' same chunk, dispatched together).
-static void xcd_patch_order(std::vector<int>& tab, int64_t tiles_x, int w) {
+// main_tiles > 0: tiles from main_tiles on (sliver workgroups) are no part of
+// the tiles_x-wide grid; they keep their order behind the generation's patches.
+static void xcd_patch_order(std::vector<int>& tab, int64_t tiles_x, int w, int64_t main_tiles = 0) {
     constexpr int kXcd = 8;
     const size_t n = tab.size() / 3;
     for (size_t g0 = 0; g0 < n;) {
@@ -1460,6 +1635,8 @@ static void xcd_patch_order(std::vector<int>& tab, int64_t tiles_x, int w) {
         std::vector<int> t;
         for (size_t i = g0; i < g1; ++i) t.push_back(tab[3 * i]);
         std::stable_sort(t.begin(), t.end(), [&](int a, int b) {
+            const bool oa = main_tiles > 0 && a >= main_tiles, ob = main_tiles > 0 && b >= main_tiles;
+            if (oa || ob) return oa != ob ? ob : a < b;
             const int64_t sa = (a % tiles_x) / w, sb = (b % tiles_x) / w;
             return sa != sb ? sa < sb : a < b;
         });
@@ -1476,28 +1653,30 @@ static void xcd_patch_order(std::vector<int>& tab, int64_t tiles_x, int w) {
 // Same-XCD x/y neighbour pairs of a table (workgroup i -> XCD i % 8, per
 // generation), and the patch width in [2, min(tiles_x, 16)] that maximises
 // them (the smallest on ties; 0 when no width beats tile-major).
-static int64_t same_xcd_pairs(const std::vector<int>& tab, int64_t tiles_x) {
+static int64_t same_xcd_pairs(const std::vector<int>& tab, int64_t tiles_x, int64_t main_tiles = 0) {
     constexpr int kXcd = 8;
     std::map<std::tuple<int, int, int>, int> where;  // (tile, first plane, planes) -> XCD
     for (size_t i = 0; i < tab.size() / 3; ++i) where[{tab[3 * i], tab[3 * i + 1], tab[3 * i + 2]}] = int(i % kXcd);
     int64_t pairs = 0;
     for (const auto& [k, x] : where) {
         const int t = std::get<0>(k);
+        if (main_tiles > 0 && t >= main_tiles) continue;  // a sliver workgroup: no place in the grid
         for (int nb : {t + 1, t + int(tiles_x)}) {
             if (nb == t + 1 && (t + 1) % tiles_x == 0) continue;
+            if (main_tiles > 0 && nb >= main_tiles) continue;
             auto it = where.find({nb, std::get<1>(k), std::get<2>(k)});
             pairs += it != where.end() && it->second == x;
         }
     }
     return pairs;
 }
-static int best_patch_width(const std::vector<int>& tab, int64_t tiles_x) {
+static int best_patch_width(const std::vector<int>& tab, int64_t tiles_x, int64_t main_tiles = 0) {
     int best_w = 0;
-    int64_t best = same_xcd_pairs(tab, tiles_x);
+    int64_t best = same_xcd_pairs(tab, tiles_x, main_tiles);
     for (int w = 2; w <= std::min<int64_t>(tiles_x, 16); ++w) {
         std::vector<int> t = tab;
-        xcd_patch_order(t, tiles_x, w);
-        const int64_t p = same_xcd_pairs(t, tiles_x);
+        xcd_patch_order(t, tiles_x, w, main_tiles);
+        const int64_t p = same_xcd_pairs(t, tiles_x, main_tiles);
         if (p > best) best = p, best_w = w;
     }
     return best_w;
@@ -1505,7 +1684,7 @@ static int best_patch_width(const std::vector<int>& tab, int64_t tiles_x) {
 
 int packed_schedule(const void* kern, int dev, int64_t tiles, int64_t nz, int K, int fill, int slots, int zc,
                     hipStream_t s, bool dry, const int** sched, int64_t* nb, std::atomic<int>** verdict,
-                    bool faces_out, int64_t tiles_x, int xcd_w) {
+                    bool faces_out, int64_t tiles_x, int xcd_w, int64_t main_tiles) {
     // Only grids of few tiles: with more than 2 tiles per slot the equal
     // chunks already fill the rounds (2048^2 x 512 fp64: packed 1312 vs 1315
     // Gcell/s), and the search would cost host time at the first launch.
@@ -1522,7 +1701,7 @@ int packed_schedule(const void* kern, int dev, int64_t tiles, int64_t nz, int K,
         const int* d = nullptr;
         int64_t n = 0;
         const int rc = packed_schedule(kern, dev, tiles, nz, K, fill, slots, zc, s, false, &d, &n, nullptr, faces_out,
-                                       tiles_x, xcd_w == 0 ? -1 : 0);
+                                       tiles_x, xcd_w == 0 ? -1 : 0, main_tiles);
         sibling = false;
         if (rc != STENCIL_OK) return rc;
     }
@@ -1534,24 +1713,26 @@ int packed_schedule(const void* kern, int dev, int64_t tiles, int64_t nz, int K,
     };
     static std::mutex mu;
     // map nodes never move: the verdict's address stays valid for the process
-    static std::map<std::tuple<const void*, int, int64_t, int64_t, int, int, int, int>, Entry> cache;
+    static std::map<std::tuple<const void*, int, int64_t, int64_t, int, int, int, int, int64_t>, Entry> cache;
     std::unique_lock<std::mutex> lock(mu);
     // STENCIL_TK_PACK_LC (experiments): chunks of exactly this many planes,
     // used whatever the model says
     const int force_lc = senv_int("STENCIL_TK_PACK_LC", 0);
     if (tiles_x <= 0) xcd_w = 0;
     int xcd_w_used = xcd_w;  // xcd_w < 0: chosen below (best_patch_width)
-    const auto key = std::make_tuple(kern, dev, tiles, nz, K, slots, force_lc, xcd_w);
+    const auto key = std::make_tuple(kern, dev, tiles, nz, K, slots, force_lc, xcd_w, main_tiles);
     auto hit = cache.find(key);
     if (hit == cache.end()) {
         std::vector<int> best_tab;
         int64_t base = 0, best = 0;
-        pack_search(tiles, nz, fill, slots, zc, force_lc, &best_tab, &base, &best);
+        if (main_tiles > 0) sliver_pack_search(tiles, main_tiles, nz, fill, slots, zc, force_lc, &best_tab, &base, &best);
+        else pack_search(tiles, nz, fill, slots, zc, force_lc, &best_tab, &base, &best);
         hit = cache.try_emplace(key).first;
         if (faces_out && !best_tab.empty() && !faces_outward(best_tab, nz)) best_tab.clear();
-        if (xcd_w < 0 && !best_tab.empty()) xcd_w_used = best_patch_width(best_tab, tiles_x);
-        if (xcd_w_used > 0 && !best_tab.empty()) xcd_patch_order(best_tab, tiles_x, xcd_w_used);
-        if (!best_tab.empty() && (best * 50 < base * 49 || force_lc > 0)) {
+        if (xcd_w < 0 && !best_tab.empty()) xcd_w_used = best_patch_width(best_tab, tiles_x, main_tiles);
+        if (xcd_w_used > 0 && !best_tab.empty()) xcd_patch_order(best_tab, tiles_x, xcd_w_used, main_tiles);
+        // (sliver mode: the table stands without the 2 % rule, pack_search)
+        if (!best_tab.empty() && (best * 50 < base * 49 || force_lc > 0 || main_tiles > 0)) {
             hit->second.workgroups = int64_t(best_tab.size() / 3);
             hit->second.host = std::move(best_tab);
         }
@@ -1834,6 +2015,34 @@ int stencil_pack_table(int64_t tiles, int64_t tiles_x, int64_t planes, int32_t f
     if (tab.empty() || best * 50 >= base * 49) tab.clear();
     if (xcd_width < 0 && !tab.empty()) xcd_width = best_patch_width(tab, tiles_x);
     if (xcd_width > 0 && !tab.empty()) xcd_patch_order(tab, tiles_x, xcd_width);
+    const int64_t n = int64_t(tab.size() / 3);
+    if (table)
+        for (int64_t i = 0; i < std::min(n, capacity) * 3; ++i) table[i] = tab[size_t(i)];
+    if (workgroups) *workgroups = n;
+    clear_error();
+    return STENCIL_OK;
+}
+int stencil_sliver_table(int64_t nx, int64_t ny, int64_t planes, int32_t slots, int32_t chunk_planes, int32_t xcd_width,
+                         int64_t* geometry, int32_t* table, int64_t capacity, int64_t* workgroups) {
+    using namespace stencil;
+    using Tl = DefaultShape<double, 4>::Tile;
+    constexpr int K = 4;
+    if (nx <= 0 || ny <= 0 || planes <= 0 || slots <= 0 || chunk_planes < 0 || xcd_width < -1 ||
+        planes > (int64_t(1) << 30))
+        return set_error(STENCIL_EINVAL, "sliver table: nx, ny, planes, slots > 0, chunk_planes >= 0, xcd_width >= -1");
+    int64_t main_tiles = 0, tiles = 0;
+    const bool on = sliver_geometry(nx, ny, Tl::TX, Tl::TY, Tl::XR, slots, &main_tiles, &tiles);
+    const int64_t gx = (nx + Tl::TX - 1) / Tl::TX, gy = (ny + Tl::TY - 1) / Tl::TY;
+    if (geometry) geometry[0] = gx, geometry[1] = gy, geometry[2] = on ? main_tiles : 0, geometry[3] = on ? tiles : 0;
+    std::vector<int> tab;
+    if (on) {
+        const int64_t chunks = whole_chunk_count(tiles, planes, K, slots);
+        int64_t base = 0, best = 0;
+        sliver_pack_search(tiles, main_tiles, planes, 2 * K, slots, int((planes + chunks - 1) / chunks), chunk_planes,
+                           &tab, &base, &best);
+        if (xcd_width < 0 && !tab.empty()) xcd_width = best_patch_width(tab, gx - 1, main_tiles);
+        if (xcd_width > 0 && !tab.empty()) xcd_patch_order(tab, gx - 1, xcd_width, main_tiles);
+    }
     const int64_t n = int64_t(tab.size() / 3);
     if (table)
         for (int64_t i = 0; i < std::min(n, capacity) * 3; ++i) table[i] = tab[size_t(i)];
