@@ -37,8 +37,10 @@ HOST_HDRS := $(wildcard stencil_amd/csrc/host/*.hpp)
 
 # test infrastructure: slab_core.hpp's round logic on a CPU fake device (sweeps by the oracle)
 FAKE := tests/cpu_slab/libslab_fake.so
+# the same fake device with a source sweep: slab_core.hpp's source rounds (tests/cpu_slab_source/)
+FAKE_SRC := tests/cpu_slab_source/libslab_fake_source.so
 
-all: $(LIB) $(LIB_DBG) $(CLI) oracle $(FAKE)
+all: $(LIB) $(LIB_DBG) $(CLI) oracle $(FAKE) $(FAKE_SRC)
 
 $(OBJ)/%.o: stencil_amd/csrc/%.hip $(wildcard stencil_amd/csrc/*.hpp) include/stencil_hip.h
 	@mkdir -p $(OBJ)
@@ -98,8 +100,13 @@ $(FAKE): tests/cpu_slab/fake_dev.cpp stencil_amd/csrc/slab_core.hpp stencil_amd/
 	$(CXX) $(CXXFLAGS) -fPIC -shared -pthread -Istencil_amd/csrc -Ioracle -o $@ $< -Loracle -loracle \
 	    -Wl,-rpath,'$$ORIGIN/../../oracle'
 
+$(FAKE_SRC): tests/cpu_slab_source/fake_source.cpp tests/cpu_slab/fake_dev.cpp stencil_amd/csrc/slab_core.hpp \
+             stencil_amd/csrc/errors.hpp include/stencil_hip.h oracle/liboracle.so
+	$(CXX) $(CXXFLAGS) -fPIC -shared -pthread -Istencil_amd/csrc -Ioracle -o $@ $< -Loracle -loracle \
+	    -Wl,-rpath,'$$ORIGIN/../../oracle'
+
 clean:
-	rm -rf build $(LIB) $(LIB_DBG) $(FAKE)
+	rm -rf build $(LIB) $(LIB_DBG) $(FAKE) $(FAKE_SRC)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -86,6 +86,9 @@ int stencil_last_error(void);
  * STENCIL_SLAB_GATE=0 (face-signalled rounds wait for the exchange stream's
  * event before each launch instead of gating the launch's halo-reading
  * workgroups on the exchange-completion word: stencil_slab_round_info),
+ * STENCIL_SLAB_SOURCE_SIGNAL=0 (the full source rounds of a face-signalled
+ * slab job, stencil_slab_run_source, take the boundary + interior form instead
+ * of one face-signalled source launch: stencil_slab_source_round_form),
  * STENCIL_UNTIL_FUSED=0 (stencil_iterate_until checks every block with a
  * single sweep and stencil_diff_norms' kernels instead of the checking K-step
  * launch, stencil_sweepk_update_max: the A/B lever and the fallback). */
@@ -520,6 +523,40 @@ int stencil_iterate_until_source(const stencil_layout* l, void* a, void* b, cons
                                  void* stream, uint32_t* iterations_done, int* final_in_b,
                                  double* last_norm, int* converged, float* elapsed_ms);
 
+/* Source launches on slab layouts (the launches of stencil_slab_run_source).
+ * stencil_sweepk_source_halo is stencil_sweepk_source for layouts that may
+ * carry STENCIL_HALO_LO / STENCIL_HALO_HI: `src` has the same layout, halo
+ * planes included.  With flags it needs halo >= steps (as stencil_sweepk);
+ * with flags == 0 it is bitwise stencil_sweepk_source.  On a halo side the
+ * launch advances the halo planes on chip, as the plain kernel does: stage s
+ * of K = steps is computed for planes [-(K - s), nz + K - s) there, and each
+ * advanced halo cell gets `src` of its own plane.  The launch therefore reads
+ * `src` on planes [begin - (K - 1), end + K - 1), clipped to
+ * [-(K - 1), nz + K - 1) on a halo side and to [0, nz) on a Dirichlet side: no
+ * value of src's planes -K or nz + K - 1, of its x/y ghost ring or padding, or
+ * of its z ghost planes on a Dirichlet side reaches a result.  It stores the
+ * interior cells of [begin, end) of `out` and nothing else.  steps = 1 reads
+ * the halo planes of `in` and advances none.
+ *   stencil_sweepk_signal_source / _gated: stencil_sweepk_signal / _gated with
+ * the source (steps 3 or 4): `out` is bitwise stencil_sweepk_source_halo's,
+ * the face counters, the face signal and the halo gate are exactly
+ * stencil_sweepk_signal's.  The strips are narrower than the plain source
+ * launch's where the signalling code needs the registers (K = 4: 4 rows per
+ * strip instead of 5), so *signals_per_face differs from the plain launch's.
+ * STENCIL_EINVAL: as stencil_sweepk_source; signalled: steps other than 3 or
+ * 4, NULL counters, a range shorter than `steps` planes; halo < steps on a
+ * layout with halo flags.  STENCIL_EUNSUPPORTED: as stencil_sweepk_source,
+ * but for the halo flags. */
+int stencil_sweepk_source_halo(const stencil_layout* l, const void* in, void* out, const void* src,
+                               int64_t begin, int64_t end, int32_t steps, void* stream);
+int stencil_sweepk_signal_source(const stencil_layout* l, const void* in, void* out, const void* src,
+                                 int64_t begin, int64_t end, int32_t steps, uint32_t* counters,
+                                 uint64_t* face_signal, int32_t* signals_per_face, void* stream);
+int stencil_sweepk_signal_source_gated(const stencil_layout* l, const void* in, void* out, const void* src,
+                                       int64_t begin, int64_t end, int32_t steps, uint32_t* counters,
+                                       uint64_t* face_signal, uint32_t gate_need, uint32_t* release_flag,
+                                       int32_t* signals_per_face, void* stream);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,
@@ -643,6 +680,51 @@ int stencil_slab_run_until(stencil_slab_job* job, uint32_t max_iterations, uint3
                            float* elapsed_ms);
 int stencil_slab_until_plan(const stencil_problem* global, uint32_t block, int32_t norm, int64_t* rounds,
                             int32_t* fused_check);
+/* Source terms across the slabs: u' = S(u) + g on the whole global grid
+ * (Poisson solves over GPUs).  Scope: two-grid jobs of the 3D 7-point star,
+ * r = 1, naive order, kernel AUTO or TEMPORALK.
+ *   stencil_slab_set_source: `host` has the global shape, as
+ * stencil_slab_upload takes it; only its interior cells have meaning.  The
+ * first call allocates one source grid per slab (STENCIL_ENOMEM if one does
+ * not fit: nothing is kept and the job stays usable); afterwards each slab's
+ * source grid holds its planes and, in the halo planes of each shared face,
+ * the neighbouring slab's (wrapped with STENCIL_SLAB_PERIODIC), filled by one
+ * exchange of the source grids.  Rank mode reads only the rank's planes.  A
+ * second call replaces the values.
+ *   stencil_slab_run_source: stencil_slab_run with the source.  Rounds take
+ * Ks = min(K, STENCIL_SOURCE_MAX_STEPS) sweeps, the remainder as one shorter
+ * round; the halo depth stays K.  Results are bitwise those of
+ * stencil_iterate_source on one grid, and it may alternate freely with
+ * stencil_slab_run.  A full round of a face-signalled job with Ks = K is one
+ * stencil_sweepk_signal_source launch per slab -- gated when the job is and
+ * the launch's own tiles meet the gate's rule, else waiting for the exchange's
+ * event -- unless STENCIL_SLAB_SOURCE_SIGNAL=0 or the job waits for its faces
+ * in the command processor (STENCIL_SLAB_CPWAIT=1).  Every other round --
+ * staged jobs' (their tuning state is not touched), remainders, Ks < K, slabs
+ * sharing a GPU -- is boundary + interior launches of
+ * stencil_sweepk_source_halo, or one launch with STENCIL_SLAB_SERIAL=1.
+ * stencil_slab_source_round_form reports a full source round's form
+ * (STENCIL_SLAB_FORM_SIGNALLED, _BOUNDARY_INTERIOR or _SERIAL).
+ *   stencil_slab_run_until_source: stencil_slab_run_until's arguments,
+ * stopping rule and edge cases on source rounds, always with the un-fused
+ * check: block - 1 source sweeps as run_source issues them, one round of a
+ * single source sweep, then stencil_diff_norms' kernels per slab, reduced as
+ * stencil_slab_run_until's un-fused check.  Counts, norms (bit for bit) and
+ * grid equal stencil_iterate_until_source's on one grid.
+ *   stencil_slab_source_plan (host only): *rounds = ceil(iterations / Ks),
+ * *steps = Ks.
+ * STENCIL_EINVAL: NULL arguments, a host array that is too small, run*_source
+ * before set_source, run_until's argument errors.  STENCIL_EUNSUPPORTED (the
+ * message names the restriction): STENCIL_SLAB_ROLLING jobs (one resident
+ * grid), anything but the 3D r = 1 naive 7-point star; run_until_source in
+ * rank mode.  Every host wait goes through the job's deadline. */
+int stencil_slab_set_source(stencil_slab_job* job, const void* host, int64_t host_row, int64_t host_rows);
+int stencil_slab_run_source(stencil_slab_job* job, uint32_t iterations, float* elapsed_ms);
+int stencil_slab_run_until_source(stencil_slab_job* job, uint32_t max_iterations, uint32_t check_every,
+                                  int32_t norm, double tol, uint32_t* iterations_done, double* last_norm,
+                                  int* converged, float* elapsed_ms);
+int stencil_slab_source_plan(const stencil_problem* global, uint32_t iterations, int64_t* rounds, int32_t* steps);
+int stencil_slab_source_round_form(const stencil_slab_job* job, int32_t* form);
 /* Per-plane interior sums of the current global grid (nz doubles, host). */
 int stencil_slab_plane_sums(stencil_slab_job* job, double* sums);
 /* Kernel timing for roofline figures: with timing on, every round records

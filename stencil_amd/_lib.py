@@ -19,7 +19,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "libstencil_hip_debug.so")
 API_KNOBS = ("STENCIL_TK_STEPS", "STENCIL_BOX_STEPS", "STENCIL_TK_PACK", "STENCIL_BOXK_PACK", "STENCIL_SLAB_SIGNAL",
              "STENCIL_SLAB_CPWAIT", "STENCIL_SLAB_SERIAL", "STENCIL_SLAB_XCU", "STENCIL_SLAB_XCU_EXCL",
              "STENCIL_SLAB_TIMEOUT_MS", "STENCIL_SLAB_ROLLING_OVERLAP", "STENCIL_SLAB_STAGED", "STENCIL_SLAB_GATE",
-             "STENCIL_SLAB_PLACEMENTS", "STENCIL_SLAB_XCU_ALT", "STENCIL_UNTIL_FUSED")
+             "STENCIL_SLAB_PLACEMENTS", "STENCIL_SLAB_XCU_ALT", "STENCIL_UNTIL_FUSED", "STENCIL_SLAB_SOURCE_SIGNAL")
 
 STENCIL_OK = 0
 ETIMEOUT = -6
@@ -65,6 +65,9 @@ EXPORTED_SYMBOLS = (
     "stencil_slab_run_until", "stencil_slab_until_plan",
     "stencil_sweepk_source", "stencil_iterate_source", "stencil_source_plan", "stencil_iterate_until_source",
     "stencil_sliver_table",
+    "stencil_sweepk_source_halo", "stencil_sweepk_signal_source", "stencil_sweepk_signal_source_gated",
+    "stencil_slab_set_source", "stencil_slab_run_source", "stencil_slab_run_until_source",
+    "stencil_slab_source_plan", "stencil_slab_source_round_form",
 )
 
 
@@ -120,7 +123,7 @@ def load(debug: bool | None = None) -> ctypes.CDLL:
             f"{path} is missing: the HIP extension has not been built "
             "(run `make` or `python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**signatures(), **slab_until_signatures()}.items():
+    for name, (res, args) in {**signatures(), **slab_until_signatures(), **slab_source_signatures()}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -186,6 +189,12 @@ def signatures() -> dict:
         "stencil_iterate_until_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int32, c_double,
                                                  c_void_p, POINTER(c_uint32), POINTER(c_int), POINTER(c_double),
                                                  POINTER(c_int), POINTER(c_float)]),
+        "stencil_sweepk_source_halo": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
+        "stencil_sweepk_signal_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                                 c_void_p, POINTER(c_int32), c_void_p]),
+        "stencil_sweepk_signal_source_gated": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                                       c_void_p, c_void_p, c_uint32, c_void_p, POINTER(c_int32),
+                                                       c_void_p]),
         "stencil_sweepk_geometry": (c_int, [L, c_int64, c_int64, c_int32, POINTER(c_int64), POINTER(c_int32),
                                             POINTER(c_int32)]),
         "stencil_sweepk_signal": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
@@ -242,6 +251,21 @@ def slab_until_signatures() -> dict:
         "stencil_slab_run_until": (c_int, [c_void_p, c_uint32, c_uint32, c_int32, c_double, POINTER(c_uint32),
                                            POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
         "stencil_slab_until_plan": (c_int, [POINTER(Problem), c_uint32, c_int32, POINTER(c_int64), POINTER(c_int32)]),
+    }
+
+
+def slab_source_signatures() -> dict:
+    """The slab jobs' source-term entry points.  Kept apart from signatures()
+    for the same reason as slab_until_signatures(): the fake device of
+    tests/cpu_slab/ does not have them (tests/cpu_slab_source/ binds them to
+    its own fake device)."""
+    return {
+        "stencil_slab_set_source": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
+        "stencil_slab_run_source": (c_int, [c_void_p, c_uint32, POINTER(c_float)]),
+        "stencil_slab_run_until_source": (c_int, [c_void_p, c_uint32, c_uint32, c_int32, c_double, POINTER(c_uint32),
+                                                  POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
+        "stencil_slab_source_plan": (c_int, [POINTER(Problem), c_uint32, POINTER(c_int64), POINTER(c_int32)]),
+        "stencil_slab_source_round_form": (c_int, [c_void_p, POINTER(c_int32)]),
     }
 
 

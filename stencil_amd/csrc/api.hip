@@ -338,6 +338,25 @@ int signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, 
     *slots = info.slots;
     return STENCIL_OK;
 }
+int source_signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, int steps, int64_t* tiles,
+                                  int64_t* workgroups, int* slots) {
+    LaunchInfo info;
+    tl_dry_launch = &info;
+    int nsig = 0;
+    void* fake = reinterpret_cast<void*>(uintptr_t(1));  // never touched in a dry launch
+    StripExtras x;
+    x.signal = true;
+    x.nsig = &nsig;
+    x.src = fake;
+    const int rc = launch_tkstrip_source_signal(l, nullptr, fake, begin, end, steps, x, nullptr);
+    tl_dry_launch = nullptr;
+    if (rc != STENCIL_OK) return rc;
+    if (info.steps == 0) return set_error(STENCIL_EUNSUPPORTED, "no face-signalled source launch was described");
+    *tiles = nsig;
+    *workgroups = info.workgroups;
+    *slots = info.slots;
+    return STENCIL_OK;
+}
 }  // namespace stencil
 
 extern "C" {
@@ -1331,14 +1350,17 @@ namespace stencil {
 namespace {
 
 // The problems the source sweeps cover; the message names what rules one out.
-int check_source_problem(const stencil_layout* l) {
+// (halo_ok: the entries for slab layouts -- stencil_sweepk_source_halo, stencil_sweepk_signal_source* -- take
+// layouts with halo flags; every other entry keeps refusing them)
+int check_source_problem(const stencil_layout* l, bool halo_ok = false) {
     if (int rc = check_layout(l)) return rc;
     const stencil_problem& p = l->prob;
     if (p.dims != 3) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: 3D grids only (got dims = %d)", p.dims);
     if (p.shape != STENCIL_STAR) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: the 7-point star only, not the box");
     if (p.radius != 1) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: radius 1 only (got %d)", p.radius);
     if (p.order != STENCIL_ORDER_NAIVE) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: the naive sum order only, not DMA");
-    if (p.flags != 0) return set_error(STENCIL_EUNSUPPORTED, "source sweeps: layouts without halo flags only (got %d)", p.flags);
+    if (p.flags != 0 && !halo_ok)
+        return set_error(STENCIL_EUNSUPPORTED, "source sweeps: layouts without halo flags only (got %d)", p.flags);
     if (p.kernel != STENCIL_KERNEL_AUTO && p.kernel != STENCIL_KERNEL_TEMPORALK)
         return set_error(STENCIL_EUNSUPPORTED, "source sweeps: kernel AUTO or TEMPORALK only (got %d)", p.kernel);
     return STENCIL_OK;
@@ -1378,6 +1400,73 @@ int stencil_sweepk_source(const stencil_layout* l, const void* in, void* out, co
     const int rc = launch_source(*l, in, out, src, begin, end, steps, as_stream(stream));
     if (rc == STENCIL_OK) clear_error();
     return rc;
+}
+
+// The argument checks the slab-layout source launches share (the order is part of their behaviour).
+static int source_halo_args(const stencil_layout* l, const void* in, const void* out, const void* src, int64_t begin,
+                            int64_t end) {
+    if (int rc = check_source_problem(l, true)) return rc;
+    if (!in || !out) return set_error(STENCIL_EINVAL, "null grid");
+    if (!src) return set_error(STENCIL_EINVAL, "null source grid");
+    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
+    if (src == in || src == out) return set_error(STENCIL_EINVAL, "the source grid must not be one of the field's grids");
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
+    return STENCIL_OK;
+}
+
+int stencil_sweepk_source_halo(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                               int64_t end, int32_t steps, void* stream) {
+    if (int rc = source_halo_args(l, in, out, src, begin, end)) return rc;
+    if (steps < 1 || steps > kSourceSteps)
+        return set_error(STENCIL_EINVAL, "steps must be 1..%d (got %d)", kSourceSteps, steps);
+    // (a halo side needs halo >= steps: the strip launch checks it, as stencil_sweepk's does)
+    const int rc = steps == 1 ? launch_source1(*l, in, out, src, begin, end, as_stream(stream))
+                              : launch_tkstrip_source_halo(*l, in, out, src, begin, end, steps, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+static int sweepk_signal_source(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                                int64_t end, int32_t steps, const SweepkExtras& e, void* stream) {
+    if (int rc = source_halo_args(l, in, out, src, begin, end)) return rc;
+    if (steps < 3 || steps > kSourceSteps)
+        return set_error(STENCIL_EINVAL, "face-signalled source sweeps: steps must be 3..%d (got %d)", kSourceSteps, steps);
+    if (!e.counters) return set_error(STENCIL_EINVAL, "null counters");
+    // a range shorter than `steps` planes would signal one face only
+    if (end - begin < steps)
+        return set_error(STENCIL_EINVAL, "a face-signalled range needs at least %d planes (got %lld)", steps,
+                         (long long)(end - begin));
+    int nsig = 0;
+    StripExtras x;
+    x.signal = true;
+    x.sig = e.counters;
+    x.fsig = reinterpret_cast<unsigned long long*>(e.face_signal);
+    x.nsig = &nsig;
+    x.src = src;
+    if (e.gated) {
+        x.gate.word = e.counters + 3;
+        x.gate.release = e.release_flag;
+        x.gate.need = e.gate_need;
+    }
+    return sweepk_done(launch_tkstrip_source_signal(*l, in, out, begin, end, steps, x, as_stream(stream)), nsig,
+                       e.signals_per_face);
+}
+
+int stencil_sweepk_signal_source(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                                 int64_t end, int32_t steps, uint32_t* counters, uint64_t* face_signal,
+                                 int32_t* signals_per_face, void* stream) {
+    return sweepk_signal_source(l, in, out, src, begin, end, steps,
+                                SweepkExtras{}.signalling(counters, face_signal, signals_per_face), stream);
+}
+
+int stencil_sweepk_signal_source_gated(const stencil_layout* l, const void* in, void* out, const void* src,
+                                       int64_t begin, int64_t end, int32_t steps, uint32_t* counters,
+                                       uint64_t* face_signal, uint32_t gate_need, uint32_t* release_flag,
+                                       int32_t* signals_per_face, void* stream) {
+    return sweepk_signal_source(
+        l, in, out, src, begin, end, steps,
+        SweepkExtras{}.signalling(counters, face_signal, signals_per_face).gate(gate_need, release_flag), stream);
 }
 
 int stencil_source_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches, int32_t* steps) {

@@ -204,6 +204,9 @@ int launch_tkstrip_probe(const stencil_layout& l, const void* in, void* out, int
 constexpr int kSourceSteps = 4;
 int launch_tkstrip_source(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
                           int64_t end, int steps, hipStream_t s);
+// the same launches on a layout that may carry halo flags (stencil_sweepk_source_halo: slab source rounds)
+int launch_tkstrip_source_halo(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                               int64_t end, int steps, hipStream_t s);
 // kernels_source.hip: one sweep with the source added
 int launch_source1(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
                    hipStream_t s);
@@ -238,6 +241,12 @@ struct StripExtras {
 // The default strip shapes with at least one of the extras' options
 int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,
                            const StripExtras& x, hipStream_t s);
+// kernels_strip_source.hip: the face-signalled source launch (steps 3 or 4; x.src, x.sig and, gated, x.gate)
+int launch_tkstrip_source_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
+                                 int steps, const StripExtras& x, hipStream_t s);
+// api.hip: the tiles (adds per face), workgroups and resident slots of that launch over [begin, end), by a dry launch
+int source_signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, int steps, int64_t* tiles,
+                                  int64_t* workgroups, int* slots);
 // stencil_iterate_until's rule (api.hip): the sweeps of the checking K-step launch that ends a block of
 // `block` sweeps on problem `p`, or 0 when the block keeps the un-fused check
 int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm);

@@ -311,7 +311,12 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // planes exist in both allocations); what a clamped or ghost address returns
 // is dropped by the ghost-cell selects (s < K) or never stored (s = K), and the
 // select-free segments compute such cells only in planes that never reach the
-// output.
+// output.  On a halo side (slab layouts, stencil_sweepk_source_halo) the
+// advanced halo planes take rhs of their own plane: stage s adds it on planes
+// [-(K - s), nz + K - s), so rhs is live on [-(K - 1), nz + K - 1) there.
+// SRC + SIG (stencil_sweepk_signal_source): the ring is indexed by march step
+// and load_rhs maps the march index to its plane through zr(), as load_plane
+// does, so a down-marching chunk's stages find the planes they walk.
 // SLIVER (sliver_shape() only; fast & kSliver): the last tile column stores at most
 // 16 - 2 XR = 8 columns, so one of its tiles needs 16 lanes of a region row: XR ring lanes, its
 // output columns, the ghost column x = nx, the rest unused.  A SLIVER WORKGROUP runs four such tiles
@@ -337,9 +342,9 @@ __global__ void __launch_bounds__(64 * NW)
     static_assert(!SPLIT || !TIER, "SPLIT: plain or face-signalled launches");
     static_assert(!UMAX || (!TIER && DIAG == 0 && !TK_SST && !TK_XRING8 && !TK_PROBE_NOBAR),
                   "UMAX: plain or face-signalled launches of the product shapes only");
-    static_assert(!SRC || (!SIG && !TIER && !UMAX && !HL && !SPLIT && DIAG == 0 && NS == 4 && !TK_SST && !TK_XRING8 &&
+    static_assert(!SRC || (!TIER && !UMAX && !HL && !SPLIT && DIAG == 0 && NS == 4 && !TK_SST && !TK_XRING8 &&
                            !TK_PROBE_NOBAR),
-                  "SRC: plain launches of the source shapes only");
+                  "SRC: plain or face-signalled launches of the source shapes only");
     constexpr bool SST = Tl::SSTS && !SIG && !TIER && !HL;
     constexpr int NI = (RY + 1) / 2;  // SST: row pairs per strip
     typedef T V4T __attribute__((ext_vector_type(4)));
@@ -610,8 +615,12 @@ __global__ void __launch_bounds__(64 * NW)
             }
         }
     };
-    // SRC: one plane of the source grid, clamped like the input's
-    auto load_rhs = [&](VT (&d)[RY], int z) {
+    // SRC: the source grid's plane of march index m (as load_plane: a down-marching chunk's ring follows
+    // the march), clamped like the input's
+    auto load_rhs = [&](VT (&d)[RY], int m) {
+        // (`if constexpr`: the up-marching instances keep their code to the instruction)
+        int z = m;
+        if constexpr (REV) z = zr(m);
         const int zz = z < zfirst ? zfirst : (z > zlast ? zlast : z);
         const char* base = rsrc + int64_t(zz) * plane * int64_t(sizeof(T));
 #pragma unroll
@@ -1459,6 +1468,18 @@ int launch_tkstrip_source(const stencil_layout& l, const void* in, void* out, co
                           int64_t end, int steps, hipStream_t s) {
     if (!temporal2_supports(l.prob) || (l.prob.flags & (STENCIL_HALO_LO | STENCIL_HALO_HI)))
         return set_error(STENCIL_EUNSUPPORTED, "source sweeps cover the 3D r=1 naive 7-point star without halo flags");
+    return launch_tkstrip_source_halo(l, in, out, src, begin, end, steps, s);
+}
+
+// The same shapes on a layout that may carry halo flags (stencil_sweepk_source_halo): halo_lo / halo_hi are
+// run-time arguments of the kernel, the source ring's loads clamp to the planes the field's loads clamp to
+// (both grids have the layout's halo planes), and launch_st's halo rules -- halo >= K, the one-round grid of a
+// slab launch, no packed table -- are the plain launch's.  A halo side's advanced planes take the source of
+// their own plane: stage s adds rhs(z) on planes [-(K - s), nz + K - s).
+int launch_tkstrip_source_halo(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                               int64_t end, int steps, hipStream_t s) {
+    if (!temporal2_supports(l.prob))
+        return set_error(STENCIL_EUNSUPPORTED, "source sweeps cover the 3D r=1 naive 7-point star only");
     StripExtras x;
     x.src = src;
     const bool f32 = l.prob.dtype == STENCIL_F32;
@@ -1473,6 +1494,35 @@ int launch_tkstrip_source(const stencil_layout& l, const void* in, void* out, co
         return f32 ? launch_st<SourceShape<float, 4>>(l, in, out, begin, end, s, x)
                    : launch_st<SourceShape<double, 4>>(l, in, out, begin, end, s, x);
     default: return set_error(STENCIL_EINVAL, "fused source sweeps: steps must be 2..4 (got %d)", steps);
+    }
+}
+
+// Face-signalled source launches (SRC + SIG; stencil_sweepk_signal_source): K = 3 and 4.  The signalling
+// code and the down-marching segment cost registers on top of the source ring, so the rows per strip are the
+// largest count not above the plain source shape's with no scratch: K = 3 keeps its 6 rows (241 fp32 / 237
+// fp64 VGPRs), K = 4 drops to 4 (214 / 188 VGPRs, 24-row tiles) -- with 5 rows both spill (256 VGPRs and 16 /
+// 8 B of scratch per lane).  TK_SRCSIG_ROWS: the compile-time probe of that choice, rows by [fp64][K - 3]
+// (DESIGN.md §5.7 has the table).  No shape may use scratch.
+#ifndef TK_SRCSIG_ROWS
+#define TK_SRCSIG_ROWS {{6, 4}, {6, 4}}
+#endif
+constexpr int kSourceSignalRows[2][2] = TK_SRCSIG_ROWS;
+template <typename T, int K>
+using SourceSignalShape = Shape<T, sizeof(T) == 8 ? 1 : 2, kSourceSignalRows[sizeof(T) == 8][K - 3], 8, K, kSrc | kSig>;
+
+int launch_tkstrip_source_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
+                                 int steps, const StripExtras& x, hipStream_t s) {
+    if (!temporal2_supports(l.prob))
+        return set_error(STENCIL_EUNSUPPORTED, "face-signalled source sweeps cover the 3D r=1 naive 7-point star only");
+    const bool f32 = l.prob.dtype == STENCIL_F32;
+    switch (steps) {
+    case 3:
+        return f32 ? launch_st<SourceSignalShape<float, 3>>(l, in, out, begin, end, s, x)
+                   : launch_st<SourceSignalShape<double, 3>>(l, in, out, begin, end, s, x);
+    case 4:
+        return f32 ? launch_st<SourceSignalShape<float, 4>>(l, in, out, begin, end, s, x)
+                   : launch_st<SourceSignalShape<double, 4>>(l, in, out, begin, end, s, x);
+    default: return set_error(STENCIL_EINVAL, "face-signalled source sweeps: steps must be 3 or 4 (got %d)", steps);
     }
 }
 #else

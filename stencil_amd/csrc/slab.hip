@@ -395,6 +395,41 @@ struct HipDev {
         *nsig = n;
         return rc;
     }
+    // ---- source rounds (slab_core.hpp set_source / run_source) ----
+    static int sweepk_source(const stencil_layout* l, const void* in, void* out, const void* src, int64_t b, int64_t e,
+                             int k, Stream s) {
+        return stencil_sweepk_source_halo(l, in, out, src, b, e, k, s);
+    }
+    // STENCIL_SLAB_SOURCE_SIGNAL=0: the full source rounds of a face-signalled job take the boundary +
+    // interior form (the default follows the measurement in DESIGN.md §7)
+    static bool source_signal_enabled() { return api_knob("STENCIL_SLAB_SOURCE_SIGNAL", 1) != 0; }
+    // halo_gate's rule on the face-signalled source launch's own tiles
+    static bool source_halo_gate(const stencil_layout& l, int k, bool confined) {
+        if (confined) return true;
+        int64_t tiles = 0, wg = 0;
+        int slots = 0;
+        if (source_signal_launch_geometry(l, 0, l.prob.nz, k, &tiles, &wg, &slots) != STENCIL_OK) {
+            clear_error();
+            return false;
+        }
+        return slots > 0 && 2 * tiles <= slots - slots / 32;
+    }
+    static int sweepk_signal_source(const stencil_layout* l, const void* in, void* out, const void* src, int64_t b,
+                                    int64_t e, int k, uint32_t* counters, uint64_t* fsig, int* nsig, Stream s) {
+        int32_t n = 0;
+        const int rc = stencil_sweepk_signal_source(l, in, out, src, b, e, k, counters, fsig, &n, s);
+        *nsig = n;
+        return rc;
+    }
+    static int sweepk_signal_source_gated(const stencil_layout* l, const void* in, void* out, const void* src, int64_t b,
+                                          int64_t e, int k, uint32_t* counters, uint64_t* fsig, uint32_t need,
+                                          uint32_t* release, int* nsig, Stream s) {
+        int32_t n = 0;
+        if (knob("STENCIL_SLAB_GATE_SKIP", 0)) need = 0;  // as sweepk_signal_gated
+        const int rc = stencil_sweepk_signal_source_gated(l, in, out, src, b, e, k, counters, fsig, need, release, &n, s);
+        *nsig = n;
+        return rc;
+    }
     // ---- convergence checks (slab_core.hpp run_until) ----
     static int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm) {
         return stencil::until_fused_steps(p, block, norm);
@@ -662,6 +697,31 @@ int stencil_slab_until_plan(const stencil_problem* global, uint32_t block, int32
     if (fused_check) *fused_check = kf ? 1 : 0;
     stencil::clear_error();
     return STENCIL_OK;
+}
+
+int stencil_slab_set_source(stencil_slab_job* job, const void* host, int64_t host_row, int64_t host_rows) {
+    return core::set_source<HipDev>(job, host, host_row, host_rows);
+}
+
+int stencil_slab_run_source(stencil_slab_job* job, uint32_t iterations, float* elapsed_ms) {
+    const stencil::SustainedScope sustained(iterations >= stencil::kSustainedSweeps);
+    return core::run_source<HipDev>(job, iterations, elapsed_ms);
+}
+
+int stencil_slab_run_until_source(stencil_slab_job* job, uint32_t max_iterations, uint32_t check_every, int32_t norm,
+                                  double tol, uint32_t* iterations_done, double* last_norm, int* converged,
+                                  float* elapsed_ms) {
+    const stencil::SustainedScope sustained(max_iterations >= stencil::kSustainedSweeps);
+    return core::run_until_source<HipDev>(job, max_iterations, check_every, norm, tol, iterations_done, last_norm,
+                                          converged, elapsed_ms);
+}
+
+int stencil_slab_source_plan(const stencil_problem* global, uint32_t iterations, int64_t* rounds, int32_t* steps) {
+    return core::source_plan<HipDev>(global, iterations, rounds, steps);
+}
+
+int stencil_slab_source_round_form(const stencil_slab_job* job, int32_t* form) {
+    return core::source_round_form<HipDev>(job, form);
 }
 
 int stencil_slab_download(stencil_slab_job* job, void* host, int64_t host_row, int64_t host_rows) {

@@ -36,7 +36,8 @@
 // csrc/slab.hip's HipDev (HIP + RCCL, the product) and the CPU test build's
 // fake device (tests/cpu_slab/: synchronous plane copies and the oracle's
 // sweep, an in-process mailbox for send/recv), which runs this same round
-// logic at world 2/3 under `pytest -m "not gpu"`.
+// logic at world 2/3 under `pytest -m "not gpu"` (tests/cpu_slab_source/: the
+// same fake device with a source sweep, for the source rounds).
 #pragma once
 
 #include <algorithm>
@@ -121,6 +122,10 @@ struct Slab {
     void* chk_dev = nullptr;
     void* chk_host = nullptr;
     typename Dev::Event ev_word{};
+    // source rounds (set_source; allocated by its first call): the source grid g of u' = S(u) + g in the
+    // slab's own layout -- its planes, and in the `depth` halo planes of each shared face the neighbouring
+    // slabs' source planes (they never change: one exchange at set_source fills them)
+    void* src = nullptr;
 };
 
 template <class Dev>
@@ -171,6 +176,9 @@ struct Job {
     int64_t timeout_ms = 60000;
     int failed = STENCIL_OK;
     uint64_t rounds = 0;  // rounds issued (the in-flight ring's index)
+    // face-signalled source rounds of a gated job: 1 = their launches are gated too, 0 = they wait for the
+    // exchange's event (the source launch's own tiles do not meet the gate's rule), -1 = not decided yet
+    int source_gate = -1;
 };
 
 constexpr int kInflight = 8;  // rounds queued ahead of the last completed exchange
@@ -855,7 +863,7 @@ void release(JobT* j) {
         (void)Dev::set_device(s.device);
         if (s.comm) Dev::comm_destroy(s.comm);
         if (!drained) continue;
-        for (void* p : {s.a, s.b, s.xs, s.xr, s.chk_dev})
+        for (void* p : {s.a, s.b, s.xs, s.xr, s.chk_dev, s.src})
             if (p) Dev::free(p);
         if (s.chk_host) Dev::free_flag(static_cast<uint32_t*>(s.chk_host));  // pinned host memory, as the flag
         for (typename Dev::Stream st : {s.sx, s.sa, s.sb, s.sx_alt, s.sb_alt})
@@ -1539,9 +1547,19 @@ int check_round(Job<Dev>& j, int k) {
     return STENCIL_OK;
 }
 
-template <class Dev, class JobT>
+// What run_until sweeps with: the plain rounds, whose check may ride in a block's last round, or (further
+// down) the source rounds, whose check is always the un-fused one.
+template <class Dev>
+struct PlainRounds {
+    int fused(const Job<Dev>& j, uint32_t block, int32_t norm) const { return check_steps<Dev>(j.global, j.k, block, norm); }
+    int rounds(Job<Dev>& j, uint32_t sweeps) const { return plain_rounds(j, sweeps); }
+    int single(Job<Dev>& j) const { return one_round(j, 1, false); }
+};
+
+template <class Dev, class JobT, class Rounds = PlainRounds<Dev>>
 int run_until(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t norm, double tol,
-              uint32_t* iterations_done, double* last_norm, int* converged, float* elapsed_ms) {
+              uint32_t* iterations_done, double* last_norm, int* converged, float* elapsed_ms,
+              const Rounds& sweeps = Rounds{}) {
     if (!job) return set_error(STENCIL_EINVAL, "null job");
     if (check_every == 0) return set_error(STENCIL_EINVAL, "check_every must be at least 1");
     if (!(tol >= 0.0)) return set_error(STENCIL_EINVAL, "tol must be a number >= 0");
@@ -1567,9 +1585,9 @@ int run_until(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t 
     std::vector<double> planes;  // un-fused: the global per-plane maxima, then the per-plane sums
     while (done < max_iterations) {
         const uint32_t block = std::min(check_every, max_iterations - done);
-        const int kf = check_steps<Dev>(job->global, job->k, block, norm);
+        const int kf = sweeps.fused(*job, block, norm);
         if (kf) {
-            SLAB_TRY(plain_rounds(*job, block - uint32_t(kf)));
+            SLAB_TRY(sweeps.rounds(*job, block - uint32_t(kf)));
             SLAB_TRY(check_round(*job, kf));
             for (Slab<Dev>& s : job->s) {
                 SLAB_FAIL(*job, Dev::set_device(s.device));
@@ -1577,8 +1595,8 @@ int run_until(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t 
                 SLAB_FAIL(*job, Dev::to_host(s.chk_host, s.chk_dev, sizeof(uint64_t), s.sa));
             }
         } else {
-            SLAB_TRY(plain_rounds(*job, block - 1));
-            SLAB_TRY(one_round(*job, 1, false));
+            SLAB_TRY(sweeps.rounds(*job, block - 1));
+            SLAB_TRY(sweeps.single(*job));
             // the two grids now hold u^n and u^(n-1) on every slab's own planes
             for (Slab<Dev>& s : job->s) {
                 SLAB_FAIL(*job, Dev::set_device(s.device));
@@ -1634,6 +1652,204 @@ int run_until(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t 
     if (last_norm) *last_norm = last;
     if (converged) *converged = conv;
     clear_error();
+    return STENCIL_OK;
+}
+
+// ---- source rounds (stencil_slab_set_source / run_source / run_until_source) ---
+// u' = S(u) + g across the slabs: the same rounds with launches that add each slab's
+// source grid.  A round takes Ks = min(K, STENCIL_SOURCE_MAX_STEPS) sweeps, the job's halo depth stays K, and
+// a halo side's advanced planes take the neighbour's source planes from the source grid's halo planes.
+// Everything below uses Dev members the plain rounds do not (sweepk_source, ...): it is instantiated by
+// slab.hip and by the CPU test build of tests/cpu_slab_source/, never by tests/cpu_slab/.
+template <class Dev>
+struct SourceSweep {
+    int begin(Slab<Dev>&) const { return STENCIL_OK; }
+    int operator()(Slab<Dev>& s, const void* src, void* dst, int64_t b, int64_t e, int k,
+                   typename Dev::Stream st) const {
+        return Dev::sweepk_source(&s.l, src, dst, s.src, b, e, k, st);
+    }
+};
+template <class Dev>
+struct SourceSignal {
+    int begin(Slab<Dev>&) const { return STENCIL_OK; }
+    int operator()(const Job<Dev>& j, Slab<Dev>& s, const void* src, void* dst, int k, int* nsig) const {
+        if (j.gate)
+            return Dev::sweepk_signal_source_gated(&s.l, src, dst, s.src, 0, s.n, k, s.counters, s.fsig, s.xseq, s.tflag,
+                                                   nsig, s.sb);
+        return Dev::sweepk_signal_source(&s.l, src, dst, s.src, 0, s.n, k, s.counters, s.fsig, nsig, s.sb);
+    }
+};
+
+// the problems source rounds cover; the message names what rules one out
+inline int check_source_global(const stencil_problem& g) {
+    if (g.dims != 3 || g.shape != STENCIL_STAR || g.radius != 1 || g.order != STENCIL_ORDER_NAIVE ||
+        (g.kernel != STENCIL_KERNEL_AUTO && g.kernel != STENCIL_KERNEL_TEMPORALK))
+        return set_error(STENCIL_EUNSUPPORTED, "slab source rounds cover the 3D r=1 naive 7-point star (kernel AUTO or "
+                         "TEMPORALK) only, not %s", g.shape != STENCIL_STAR ? "the box" : "this problem");
+    return STENCIL_OK;
+}
+template <class Dev>
+int check_source_job(const Job<Dev>& j, bool need_source) {
+    if (j.margin)
+        return set_error(STENCIL_EUNSUPPORTED, "rolling slab jobs (STENCIL_SLAB_ROLLING) keep one resident grid: source "
+                         "rounds need the two-grid job");
+    SLAB_TRY(check_source_global(j.global));
+    if (need_source)
+        for (const Slab<Dev>& s : j.s)
+            if (!s.src) return set_error(STENCIL_EINVAL, "no source term: call stencil_slab_set_source first");
+    return STENCIL_OK;
+}
+
+// Sweeps of a full source round.
+template <class Dev>
+inline int source_steps(const Job<Dev>& j) { return std::min<int>(j.k, STENCIL_SOURCE_MAX_STEPS); }
+
+// The form of a full source round.  Face-signalled where the job's rounds are, with three more conditions:
+// the round takes the job's K sweeps (a launch signals a face once its Ks planes are stored, and the
+// exchange sends K), the exchange does not wait on a HIP signal word in the command processor (the kernel
+// finds the add that completes a face by the running count modulo the launch's tiles, and the source launch's
+// tile count is not the plain launch's: check_round above), and STENCIL_SLAB_SOURCE_SIGNAL allows it.
+template <class Dev>
+int source_round_form_of(const Job<Dev>& j) {
+    const int ks = source_steps(j);
+    if (j.signal && ks == j.k && ks >= 3 && !j.s.empty() && !j.s[0].fsig && Dev::source_signal_enabled())
+        return STENCIL_SLAB_FORM_SIGNALLED;
+    return j.serial ? STENCIL_SLAB_FORM_SERIAL : STENCIL_SLAB_FORM_BOUNDARY_INTERIOR;
+}
+
+// One source round of `k` sweeps.  A staged job's source rounds take slab_round's form (its tuning state is
+// not touched), as do remainder rounds and jobs whose slabs share a GPU.
+template <class Dev>
+int one_source_round(Job<Dev>& j, int k, bool full) {
+    SLAB_TRY(throttle(j));
+    if (full && source_round_form_of(j) == STENCIL_SLAB_FORM_SIGNALLED) {
+        // A gated job gates these launches only where the source launch's own waiting chunks (its tiles are
+        // smaller than the plain launch's) can never hold every CU the exchange's kernels need
+        // (Dev::halo_gate's rule); otherwise this round is an ungated face-signalled one: its exchange
+        // posts no completion number, and the rounds around it wait for the exchange's event.
+        if (j.gate && j.source_gate < 0) {
+            bool fits = true;
+            for (Slab<Dev>& s : j.s) {
+                SLAB_FAIL(j, Dev::set_device(s.device));
+                fits = fits && Dev::source_halo_gate(s.l, k, j.confine);
+            }
+            j.source_gate = fits ? 1 : 0;
+        }
+        const bool job_gate = j.gate;
+        j.gate = job_gate && j.source_gate == 1;
+        if (!j.gate) j.gate_chain = false;
+        const int rc = slab_round_signal(j, k, SourceSignal<Dev>{});  // (sets gate_chain from this round's gate)
+        j.gate = job_gate;
+        SLAB_FAIL(j, rc);
+    } else {
+        j.gate_chain = false;  // only a gated launch may follow a gated launch unsynchronised
+        SLAB_FAIL(j, slab_round(j, k, SourceSweep<Dev>{}));
+    }
+    SLAB_FAIL(j, mark_round(j));
+    return STENCIL_OK;
+}
+
+// `sweeps` source sweeps: full rounds of Ks, then one shorter round.
+template <class Dev>
+int source_rounds(Job<Dev>& j, uint32_t sweeps) {
+    uint32_t done = 0;
+    const uint32_t k = uint32_t(source_steps(j));
+    for (; done + k <= sweeps; done += k) SLAB_TRY(one_source_round(j, int(k), true));
+    if (done < sweeps) SLAB_TRY(one_source_round(j, int(sweeps - done), false));
+    return STENCIL_OK;
+}
+template <class Dev>
+struct SourceRounds {
+    int fused(const Job<Dev>&, uint32_t, int32_t) const { return 0; }  // the check is always the un-fused one
+    int rounds(Job<Dev>& j, uint32_t sweeps) const { return source_rounds(j, sweeps); }
+    int single(Job<Dev>& j) const { return one_source_round(j, 1, false); }
+};
+
+// The host array has the global shape (as upload's); only interior cells have meaning.  Each slab's source
+// grid takes its planes (with the array's ghost cells, which no sweep reads), then ONE exchange of the source
+// grids fills the halo planes with the neighbours' -- the field's own exchange, on the source grids.
+template <class Dev, class JobT>
+int set_source(JobT* job, const void* host, int64_t host_row, int64_t host_rows) {
+    if (!job || !host) return set_error(STENCIL_EINVAL, "null argument");
+    SLAB_TRY(check_source_job(*job, false));
+    const stencil_problem& g = job->global;
+    if (host_row < g.nx + 2 * g.radius || host_rows < g.ny + 2 * g.radius)
+        return set_error(STENCIL_EINVAL, "host array too small");
+    SLAB_TRY(sync_bounded(*job));
+    // all or nothing: a grid that does not fit leaves the job as it was
+    std::vector<void*> fresh(job->s.size(), nullptr);
+    int rc = STENCIL_OK;
+    for (size_t i = 0; i < job->s.size() && rc == STENCIL_OK; ++i) {
+        Slab<Dev>& s = job->s[i];
+        if (s.src) continue;
+        if ((rc = Dev::set_device(s.device)) == STENCIL_OK) rc = Dev::alloc(s.l.bytes + 256, &fresh[i]);
+    }
+    if (rc != STENCIL_OK) {
+        for (size_t i = 0; i < fresh.size(); ++i)
+            if (fresh[i] && Dev::set_device(job->s[i].device) == STENCIL_OK) Dev::free(fresh[i]);
+        return rc;
+    }
+    for (size_t i = 0; i < fresh.size(); ++i)
+        if (fresh[i]) job->s[i].src = fresh[i];
+    const size_t es = g.dtype == STENCIL_F64 ? 8 : 4;
+    for (Slab<Dev>& s : job->s) {
+        SLAB_FAIL(*job, Dev::set_device(s.device));
+        const char* h = static_cast<const char*>(host) + size_t(s.first) * size_t(host_row * host_rows) * es;
+        SLAB_FAIL(*job, Dev::upload(&s.l, s.src, h, host_row, host_rows, s.sa));
+    }
+    // the exchange moves the faces of the grid at position 0: for its duration that is the source grid
+    for (Slab<Dev>& s : job->s) std::swap(s.a, s.src);
+    rc = exchange(*job, 0);
+    for (Slab<Dev>& s : job->s) std::swap(s.a, s.src);
+    SLAB_FAIL(*job, rc);
+    SLAB_TRY(sync_bounded(*job));
+    clear_error();
+    return STENCIL_OK;
+}
+
+template <class Dev, class JobT>
+int run_source(JobT* job, uint32_t iterations, float* elapsed_ms) {
+    if (!job) return set_error(STENCIL_EINVAL, "null job");
+    SLAB_TRY(check_source_job(*job, true));
+    SLAB_TRY(sync_bounded(*job));
+    const auto t0 = std::chrono::steady_clock::now();
+    SLAB_TRY(source_rounds(*job, iterations));
+    SLAB_TRY(sync_bounded(*job));
+    if (job->signal) SLAB_FAIL(*job, check_signal_timeouts(*job));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (elapsed_ms) *elapsed_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    clear_error();
+    return STENCIL_OK;
+}
+
+template <class Dev, class JobT>
+int run_until_source(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t norm, double tol,
+                     uint32_t* iterations_done, double* last_norm, int* converged, float* elapsed_ms) {
+    if (!job) return set_error(STENCIL_EINVAL, "null job");
+    SLAB_TRY(check_source_job(*job, true));
+    return run_until<Dev, JobT, SourceRounds<Dev>>(job, max_iterations, check_every, norm, tol, iterations_done, last_norm,
+                                                   converged, elapsed_ms, SourceRounds<Dev>{});
+}
+
+// ceil(iterations / Ks) rounds of Ks = min(K, STENCIL_SOURCE_MAX_STEPS) sweeps (host only).
+template <class Dev>
+int source_plan(const stencil_problem* global, uint32_t iterations, int64_t* rounds, int32_t* steps) {
+    if (!global) return set_error(STENCIL_EINVAL, "null problem");
+    stencil_problem g;
+    SLAB_TRY(check_global<Dev>(global, &g, 0));
+    SLAB_TRY(check_source_global(g));
+    const int ks = std::min<int>(Dev::fuse_depth(g), STENCIL_SOURCE_MAX_STEPS);
+    if (rounds) *rounds = int64_t(iterations / uint32_t(ks)) + (iterations % uint32_t(ks) ? 1 : 0);
+    if (steps) *steps = ks;
+    clear_error();
+    return STENCIL_OK;
+}
+
+template <class Dev, class JobT>
+int source_round_form(const JobT* job, int32_t* form) {
+    if (!job || !form) return set_error(STENCIL_EINVAL, "null argument");
+    SLAB_TRY(check_source_job(*job, false));
+    *form = source_round_form_of(*job);
     return STENCIL_OK;
 }
 

@@ -423,6 +423,38 @@ class JacobiEngine:
                                                   ctypes.c_void_p(dst_grid.data_ptr()), self._source_ptr(), begin, end,
                                                   steps, _stream_handle(stream)), "stencil_sweepk_source", lib=self.lib)
 
+    def sweepk_source_halo(self, src_grid: torch.Tensor, dst_grid: torch.Tensor, begin: int, end: int, steps: int,
+                           stream=None) -> None:
+        """sweepk_source on a layout that may carry halo flags
+        (stencil_sweepk_source_halo): a halo side's planes are advanced on chip
+        and take the source grid's halo planes (fill them through a view of
+        self.source; set_source() writes the interior only)."""
+        _lib.check(self.lib.stencil_sweepk_source_halo(ctypes.byref(self.layout), ctypes.c_void_p(src_grid.data_ptr()),
+                                                       ctypes.c_void_p(dst_grid.data_ptr()), self._source_ptr(), begin,
+                                                       end, steps, _stream_handle(stream)),
+                   "stencil_sweepk_source_halo", lib=self.lib)
+
+    def sweepk_signal_source(self, src_grid: torch.Tensor, dst_grid: torch.Tensor, begin: int, end: int, steps: int,
+                             counters: torch.Tensor, stream=None, face_signal: "FaceSignal | None" = None,
+                             gated: bool = False, gate_need: int = 0) -> int:
+        """sweepk_signal with the source (stencil_sweepk_signal_source; steps 3
+        or 4): `dst` as sweepk_source_halo's, counters and face signal as
+        sweepk_signal's; returns adds per face.  gated: the halo-gated form
+        (stencil_sweepk_signal_source_gated), whose halo-reading workgroups
+        wait until counters[3] has reached gate_need."""
+        n = ctypes.c_int32(0)
+        args = (ctypes.byref(self.layout), ctypes.c_void_p(src_grid.data_ptr()), ctypes.c_void_p(dst_grid.data_ptr()),
+                self._source_ptr(), begin, end, steps, ctypes.c_void_p(counters.data_ptr()),
+                face_signal.ptr if face_signal is not None else None)
+        if gated:
+            _lib.check(self.lib.stencil_sweepk_signal_source_gated(*args, gate_need, None, ctypes.byref(n),
+                                                                   _stream_handle(stream)),
+                       "stencil_sweepk_signal_source_gated", lib=self.lib)
+        else:
+            _lib.check(self.lib.stencil_sweepk_signal_source(*args, ctypes.byref(n), _stream_handle(stream)),
+                       "stencil_sweepk_signal_source", lib=self.lib)
+        return int(n.value)
+
     def iterate_source(self, iterations: int, stream=None, timed: bool = False):
         """iterate() with the source added after every sweep
         (stencil_iterate_source); returns (final grid tensor, device ms or None)."""
@@ -707,6 +739,56 @@ class SlabJob:
         nx, ny, nz = self.shape
         return slab_until_plan(self.spec, nx, ny, nz, block, norm, lib=self.lib)
 
+    # u' = S(u) + g across the slabs (stencil_slab_*_source: two-grid jobs of the 3D 7-point star)
+    def set_source(self, dense: np.ndarray) -> None:
+        """The source term g, already scaled by the caller: a dense array of
+        the global shape with ghosts (the oracle layout, as upload() takes it;
+        its ghost cells are ignored) or the (nz, ny, nx) interior alone."""
+        nx, ny, nz = self.shape
+        a = np.asarray(dense)
+        if a.shape == (nz, ny, nx):
+            full = self._dense()
+            r = self.spec.radius
+            full[r:-r, r:-r, r:-r] = a
+            a = full
+        a = np.ascontiguousarray(a, dtype=self._dense().dtype)
+        if a.shape != self._dense().shape:
+            raise ValueError(f"source of shape {a.shape}: expected {(nz, ny, nx)} or {self._dense().shape}")
+        _lib.check(self.lib.stencil_slab_set_source(self.job, ctypes.c_void_p(a.ctypes.data), a.shape[2], a.shape[1]),
+                   "stencil_slab_set_source", lib=self.lib)
+
+    def run_source(self, iterations: int) -> float:
+        """`iterations` source sweeps (stencil_slab_run_source); returns the
+        host wall time of the rounds (ms)."""
+        ms = ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_slab_run_source(self.job, iterations, ctypes.byref(ms)), "stencil_slab_run_source",
+                   lib=self.lib)
+        return float(ms.value)
+
+    def run_until_source(self, tol: float, max_iterations: int, check_every: int = 100,
+                         norm: str = "max") -> "UntilResult":
+        """run_until() on source sweeps (stencil_slab_run_until_source)."""
+        done, conv = ctypes.c_uint32(0), ctypes.c_int(0)
+        last, ms = ctypes.c_double(0.0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_slab_run_until_source(self.job, max_iterations, check_every, _lib.NORM_NAMES[norm],
+                                                          tol, ctypes.byref(done), ctypes.byref(last), ctypes.byref(conv),
+                                                          ctypes.byref(ms)), "stencil_slab_run_until_source", lib=self.lib)
+        return UntilResult(None, int(done.value), bool(conv.value), float(last.value), float(ms.value))
+
+    def source_plan(self, iterations: int) -> dict:
+        """run_source(iterations) as rounds, and the sweeps of a full round
+        (stencil_slab_source_plan, host only)."""
+        nx, ny, nz = self.shape
+        return slab_source_plan(self.spec, nx, ny, nz, iterations, lib=self.lib)
+
+    def source_round_form(self) -> int:
+        """The form of a full source round: 0 boundary + interior launches,
+        1 face-signalled, 3 serial (stencil_slab_source_round_form)."""
+        f = ctypes.c_int32(-1)
+        _lib.check(self.lib.stencil_slab_source_round_form(self.job, ctypes.byref(f)), "stencil_slab_source_round_form",
+                   lib=self.lib)
+        return int(f.value)
+
     def kernel_timing(self, enable: bool) -> None:
         """Record hipEvents around slab 0's compute launch of every round from
         now on (the whole slab in face-signalled rounds, else its interior)."""
@@ -775,3 +857,14 @@ def slab_until_plan(spec: StencilSpec, nx: int, ny: int, nz: int, block: int, no
     _lib.check(lib.stencil_slab_until_plan(ctypes.byref(prob), block, _lib.NORM_NAMES[norm], ctypes.byref(rounds),
                                            ctypes.byref(fused)), "stencil_slab_until_plan", lib=lib)
     return {"rounds": int(rounds.value), "fused_check": bool(fused.value)}
+
+
+def slab_source_plan(spec: StencilSpec, nx: int, ny: int, nz: int, iterations: int, lib=None) -> dict:
+    """stencil_slab_source_plan for the global problem (host only, no job and
+    no device needed): {"rounds", "steps"}."""
+    lib = lib if lib is not None else _lib.load()
+    prob = spec.problem(nx, ny, nz)
+    rounds, steps = ctypes.c_int64(0), ctypes.c_int32(0)
+    _lib.check(lib.stencil_slab_source_plan(ctypes.byref(prob), iterations, ctypes.byref(rounds), ctypes.byref(steps)),
+               "stencil_slab_source_plan", lib=lib)
+    return {"rounds": int(rounds.value), "steps": int(steps.value)}
