@@ -60,6 +60,8 @@ $(OBJ)/kernels_strip_ilp.o: stencil_amd/csrc/kernels_strip.hip
 $(OBJ)/kernels_strip_ilp.o: HIPFLAGS += -Xarch_device -mllvm=-misched=gcn-max-ilp
 # the strip kernel's source shapes (kernels_strip_source.hip includes kernels_strip.hip), default scheduler
 $(OBJ)/kernels_strip_source.o: stencil_amd/csrc/kernels_strip.hip
+# the relaxed source shapes (kernels_strip_relax.hip includes kernels_strip.hip), default scheduler
+$(OBJ)/kernels_strip_relax.o: stencil_amd/csrc/kernels_strip.hip
 # the strip probe (debug library only): the max-ILP shapes again, as a compile-time variant
 $(OBJ)/kernels_strip_probe.o: stencil_amd/csrc/kernels_strip.hip
 $(OBJ)/kernels_strip_probe.o: HIPFLAGS += -Xarch_device -mllvm=-misched=gcn-max-ilp

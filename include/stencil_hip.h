@@ -557,6 +557,64 @@ int stencil_sweepk_signal_source_gated(const stencil_layout* l, const void* in, 
                                        uint64_t* face_signal, uint32_t gate_need, uint32_t* release_flag,
                                        int32_t* signals_per_face, void* stream);
 
+/* Relaxed source sweeps: damped Jacobi, and Chebyshev or scheduled-relaxation
+ * Jacobi when the weights cycle through a schedule.  Scope, grids and the
+ * stores rule are stencil_sweepk_source's (3D 7-point star, r = 1, naive
+ * order, fp32 / fp64, flags == 0, kernel AUTO or TEMPORALK; `src` a device grid
+ * of the field's layout, for a plain smoother a grid of zeros).  One relaxed
+ * sweep with the weight omega stores, at every interior cell c of its planes,
+ *   J   = fl( fl( sum6(in, c) * avg ) + src(c) )    the source sweep's value
+ *   d   = fl( J - in(c) )
+ *   out = fl( in(c) + fl( w * d ) )                 w = omega rounded once to
+ *                                                   the grid's type
+ * four roundings after the multiply, never an fma.  Ghost cells keep their
+ * value and get neither source nor relaxation.  A launch of `steps` sweeps with
+ * the weights omegas[0 .. steps) is bitwise `steps` such sweeps in order.
+ * omega = 1 is NOT promised to equal the source sweep: fl(c + fl(J - c))
+ * differs from J in some cells (where J - c is inexact).
+ *
+ * stencil_sweepk_relax: steps in 1 .. STENCIL_SOURCE_MAX_STEPS; 2, 3 and 4 are
+ * the K-step strip kernel with its relaxation option (the weights travel as
+ * kernel arguments: no device buffer, no copy), 1 a single relaxed sweep.
+ * `omegas` is a host array of `steps` doubles.
+ * stencil_iterate_relax: ping-pong from `a` by stencil_iterate_source's plan
+ * (stencil_relax_plan, host only, equals stencil_source_plan); sweep i of the
+ * job (0-based) takes omegas[(phase + i) % period], so a caller continues a
+ * schedule across calls by passing the sweeps done so far as `phase`.
+ * stencil_iterate_until_relax: stencil_iterate_until_source's stopping rule,
+ * outputs and edge cases (max_iterations = 0, a NaN norm), always the un-fused
+ * check: block - 1 sweeps by the plan, one single relaxed sweep, then
+ * stencil_diff_norms' kernels; the schedule index runs on across blocks.  The
+ * norm is that of u^n - u^(n-1), which contains sweep n's weight: make
+ * check_every a multiple of `period`, so that every check sees the same weight.
+ * stencil_chebyshev_weights (host only): the Chebyshev schedule of `period`
+ * = P weights for the Dirichlet problem of p's extents,
+ *   rho = (cos(pi/(nx+1)) + cos(pi/(ny+1)) + cos(pi/(nz+1))) / 3,
+ *   omega_j = 1 / (1 - rho cos(pi (2j + 1) / (2P))),  j = 0 .. P-1,
+ * returned in the Lebedev-Finogenov order (perm_1 = [0]; perm_2m is perm_m with
+ * every entry p replaced by the pair p, 2m - 1 - p: P = 4 gives j = 0, 3, 1, 2),
+ * which keeps the intermediate error bounded -- in ascending j a long schedule
+ * overflows in fp32.  P is a power of two in 1 .. 64; *spectral_radius
+ * (optional) = rho.
+ * STENCIL_EINVAL: everything stencil_sweepk_source / stencil_iterate_source /
+ * stencil_iterate_until_source reject; NULL omegas; period == 0; a weight that
+ * is NaN or infinite; a period of stencil_chebyshev_weights that is not a power
+ * of two in 1 .. 64.  STENCIL_EUNSUPPORTED (the message names the restriction):
+ * as stencil_sweepk_source, halo flags included. */
+int stencil_sweepk_relax(const stencil_layout* l, const void* in, void* out, const void* src,
+                         int64_t begin, int64_t end, int32_t steps, const double* omegas, void* stream);
+int stencil_iterate_relax(const stencil_layout* l, void* a, void* b, const void* src, uint32_t iterations,
+                          const double* omegas, uint32_t period, uint32_t phase, void* stream,
+                          int* final_in_b, float* elapsed_ms);
+int stencil_iterate_until_relax(const stencil_layout* l, void* a, void* b, const void* src,
+                                uint32_t max_iterations, uint32_t check_every, int32_t norm, double tol,
+                                const double* omegas, uint32_t period, uint32_t phase, void* stream,
+                                uint32_t* iterations_done, int* final_in_b, double* last_norm,
+                                int* converged, float* elapsed_ms);
+int stencil_relax_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches, int32_t* steps);
+int stencil_chebyshev_weights(const stencil_problem* p, int32_t period, double* omegas,
+                              double* spectral_radius);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,

@@ -68,6 +68,8 @@ EXPORTED_SYMBOLS = (
     "stencil_sweepk_source_halo", "stencil_sweepk_signal_source", "stencil_sweepk_signal_source_gated",
     "stencil_slab_set_source", "stencil_slab_run_source", "stencil_slab_run_until_source",
     "stencil_slab_source_plan", "stencil_slab_source_round_form",
+    "stencil_sweepk_relax", "stencil_iterate_relax", "stencil_iterate_until_relax", "stencil_relax_plan",
+    "stencil_chebyshev_weights",
 )
 
 
@@ -189,6 +191,15 @@ def signatures() -> dict:
         "stencil_iterate_until_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int32, c_double,
                                                  c_void_p, POINTER(c_uint32), POINTER(c_int), POINTER(c_double),
                                                  POINTER(c_int), POINTER(c_float)]),
+        "stencil_sweepk_relax": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, POINTER(c_double),
+                                         c_void_p]),
+        "stencil_iterate_relax": (c_int, [L, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_double), c_uint32,
+                                          c_uint32, c_void_p, POINTER(c_int), POINTER(c_float)]),
+        "stencil_iterate_until_relax": (c_int, [L, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int32, c_double,
+                                                POINTER(c_double), c_uint32, c_uint32, c_void_p, POINTER(c_uint32),
+                                                POINTER(c_int), POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
+        "stencil_relax_plan": (c_int, [L, c_uint32, POINTER(c_int64), POINTER(c_int32)]),
+        "stencil_chebyshev_weights": (c_int, [P, c_int32, POINTER(c_double), POINTER(c_double)]),
         "stencil_sweepk_source_halo": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
         "stencil_sweepk_signal_source": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p,
                                                  c_void_p, POINTER(c_int32), c_void_p]),

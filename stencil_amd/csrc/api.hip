@@ -1585,6 +1585,209 @@ int stencil_iterate_until_source(const stencil_layout* l, void* a, void* b, cons
     return STENCIL_OK;
 }
 
+// ---- relaxed source sweeps (include/stencil_hip.h) ----
+}  // extern "C"
+
+namespace stencil {
+namespace {
+
+// `steps` relaxed sweeps in -> out over [begin, end), sweep i with the weight w[i]: the single relaxed sweep,
+// or the strip kernel's relax shapes
+int launch_relax(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
+                 int steps, const double* w, hipStream_t s) {
+    return steps == 1 ? launch_relax1(l, in, out, src, begin, end, w[0], s)
+                      : launch_tkstrip_relax(l, in, out, src, begin, end, steps, w, s);
+}
+
+// A schedule: `period` finite weights (the job's sweep i takes omegas[(phase + i) % period])
+int check_schedule(const double* omegas, uint32_t period) {
+    if (!omegas) return set_error(STENCIL_EINVAL, "null weights (omegas)");
+    if (period == 0) return set_error(STENCIL_EINVAL, "the schedule's period must be at least 1");
+    for (uint32_t i = 0; i < period; ++i)
+        if (!std::isfinite(omegas[i]))
+            return set_error(STENCIL_EINVAL, "weight %u of the schedule is not a finite number", i);
+    return STENCIL_OK;
+}
+
+// The relaxed job's launches from `a`: kSourceSteps sweeps each, then the remainder as one shorter launch;
+// the job's sweep i takes omegas[(phase + i) % period].  *in_b: where the result is.
+int relax_launches(const stencil_layout& l, void* a, void* b, const void* src, uint32_t iterations, const double* omegas,
+                   uint32_t period, uint64_t phase, hipStream_t s, int* in_b) {
+    const int64_t n = stencil_slow_extent(&l);
+    void* in = a;
+    void* out = b;
+    for (uint32_t i = 0; i < iterations;) {
+        const uint32_t k = std::min<uint32_t>(kSourceSteps, iterations - i);
+        double w[kSourceSteps];
+        for (uint32_t j = 0; j < k; ++j) w[j] = omegas[(phase + i + j) % period];
+        if (int rc = launch_relax(l, in, out, src, 0, n, int(k), w, s)) return rc;
+        std::swap(in, out);
+        i += k;
+    }
+    *in_b = in == b ? 1 : 0;
+    return STENCIL_OK;
+}
+
+}  // namespace
+}  // namespace stencil
+
+extern "C" {
+
+int stencil_sweepk_relax(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                         int64_t end, int32_t steps, const double* omegas, void* stream) {
+    if (int rc = check_source_problem(l)) return rc;
+    if (!in || !out) return set_error(STENCIL_EINVAL, "null grid");
+    if (!src) return set_error(STENCIL_EINVAL, "null source grid");
+    if (in == out) return set_error(STENCIL_EINVAL, "in-place sweeps are not supported");
+    if (src == in || src == out) return set_error(STENCIL_EINVAL, "the source grid must not be one of the field's grids");
+    if (steps < 1 || steps > kSourceSteps)
+        return set_error(STENCIL_EINVAL, "steps must be 1..%d (got %d)", kSourceSteps, steps);
+    if (begin < 0 || end > stencil_slow_extent(l) || begin > end)
+        return set_error(STENCIL_EINVAL, "sweep range out of bounds");
+    if (int rc = check_schedule(omegas, uint32_t(steps))) return rc;
+    const int rc = launch_relax(*l, in, out, src, begin, end, steps, omegas, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+int stencil_relax_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches, int32_t* steps) {
+    return stencil_source_plan(l, iterations, launches, steps);
+}
+
+int stencil_iterate_relax(const stencil_layout* l, void* a, void* b, const void* src, uint32_t iterations,
+                          const double* omegas, uint32_t period, uint32_t phase, void* stream, int* final_in_b,
+                          float* elapsed_ms) {
+    if (int rc = check_source_job(l, a, b, src)) return rc;
+    if (int rc = check_schedule(omegas, period)) return rc;
+    hipStream_t s = as_stream(stream);
+    const SustainedScope sustained(iterations >= kSustainedSweeps);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (elapsed_ms) {
+        STENCIL_HIP_CHECK(hipEventCreate(&e0));
+        STENCIL_HIP_CHECK(hipEventCreate(&e1));
+        STENCIL_HIP_CHECK(hipEventRecord(e0, s));
+    }
+    int fin = 0;
+    int rc = relax_launches(*l, a, b, src, iterations, omegas, period, phase, s, &fin);
+    if (elapsed_ms) {
+        if (rc == STENCIL_OK) {
+            hipError_t e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            if (e == hipSuccess) e = hipEventElapsedTime(elapsed_ms, e0, e1);
+            if (e != hipSuccess) rc = set_error(STENCIL_EHIP, "relaxed job timing: %s", hipGetErrorString(e));
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    if (rc != STENCIL_OK) return rc;
+    if (final_in_b) *final_in_b = fin;
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_iterate_until_relax(const stencil_layout* l, void* a, void* b, const void* src, uint32_t max_iterations,
+                                uint32_t check_every, int32_t norm, double tol, const double* omegas, uint32_t period,
+                                uint32_t phase, void* stream, uint32_t* iterations_done, int* final_in_b,
+                                double* last_norm, int* converged, float* elapsed_ms) {
+    if (int rc = check_source_job(l, a, b, src)) return rc;
+    if (check_every == 0) return set_error(STENCIL_EINVAL, "check_every must be at least 1");
+    if (!(tol >= 0.0)) return set_error(STENCIL_EINVAL, "tol must be a number >= 0");
+    if (norm != STENCIL_NORM_MAX && norm != STENCIL_NORM_L2) return set_error(STENCIL_EINVAL, "bad norm %d", norm);
+    if (int rc = check_schedule(omegas, period)) return rc;
+    hipStream_t s = as_stream(stream);
+    const int64_t n = stencil_slow_extent(l);
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    NormScratch sc;
+    sc.s = s;
+    std::vector<double> host(size_t(2 * n));
+    uint32_t done = 0;
+    int conv = 0;
+    double last = std::numeric_limits<double>::infinity();
+    void* cur = a;  // the grid that holds the newest sweep
+    void* old = b;
+    if (max_iterations > 0) {
+        if (elapsed_ms) {
+            STENCIL_HIP_CHECK(hipEventCreate(&ev.e0));
+            STENCIL_HIP_CHECK(hipEventCreate(&ev.e1));
+            STENCIL_HIP_CHECK(hipEventRecord(ev.e0, s));
+        }
+        if (n > 0)
+            STENCIL_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sc.dev), size_t(diff_norms_workspace_bytes(*l, n)), s));
+    }
+    while (done < max_iterations) {
+        // block - 1 sweeps by the relaxed job's plan, then one single relaxed sweep, so that the grids hold
+        // u^(n-1) and u^n for the check; the schedule index runs on across blocks
+        const uint32_t block = std::min(check_every, max_iterations - done);
+        const uint64_t at = uint64_t(phase) + done;
+        if (block > 1) {
+            int fin = 0;
+            const SustainedScope sustained(block - 1 >= kSustainedSweeps);  // as a job of block - 1 sweeps
+            if (int rc = relax_launches(*l, cur, old, src, block - 1, omegas, period, at, s, &fin)) return rc;
+            if (fin) std::swap(cur, old);
+        }
+        const double w = omegas[(at + block - 1) % period];
+        if (int rc = launch_relax(*l, cur, old, src, 0, n, 1, &w, s)) return rc;
+        std::swap(cur, old);
+        done += block;
+        if (int rc = norms_to_host(*l, cur, old, 0, n, sc.dev, host.data(), s)) return rc;
+        last = scalar_norm(host.data(), n, norm);
+        if (last <= tol) {
+            conv = 1;
+            break;
+        }
+        if (last != last) break;
+    }
+    if (elapsed_ms) {
+        *elapsed_ms = 0.f;
+        if (ev.e0) {
+            STENCIL_HIP_CHECK(hipEventRecord(ev.e1, s));
+            STENCIL_HIP_CHECK(hipEventSynchronize(ev.e1));
+            STENCIL_HIP_CHECK(hipEventElapsedTime(elapsed_ms, ev.e0, ev.e1));
+        }
+    }
+    if (iterations_done) *iterations_done = done;
+    if (final_in_b) *final_in_b = cur == b ? 1 : 0;
+    if (last_norm) *last_norm = last;
+    if (converged) *converged = conv;
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_chebyshev_weights(const stencil_problem* p, int32_t period, double* omegas, double* spectral_radius) {
+    if (!p) return set_error(STENCIL_EINVAL, "null problem");
+    if (!omegas) return set_error(STENCIL_EINVAL, "null weights (omegas)");
+    if (period < 1 || period > 64 || (period & (period - 1)))
+        return set_error(STENCIL_EINVAL, "the period must be a power of two in 1..64 (got %d)", period);
+    if (p->dims != 3 || p->shape != STENCIL_STAR || p->radius != 1)
+        return set_error(STENCIL_EUNSUPPORTED, "Chebyshev weights: the 3D 7-point star (r = 1) only");
+    if (p->nx < 1 || p->ny < 1 || p->nz < 1) return set_error(STENCIL_EINVAL, "Chebyshev weights: empty grid");
+    const double pi = 3.141592653589793;
+    // Jacobi's spectral radius on the Dirichlet problem: its eigenvalues lie in [-rho, rho]
+    const double rho =
+        (std::cos(pi / double(p->nx + 1)) + std::cos(pi / double(p->ny + 1)) + std::cos(pi / double(p->nz + 1))) / 3.0;
+    // the Lebedev-Finogenov order: perm_1 = [0]; perm_2m = perm_m with every p replaced by (p, 2m - 1 - p)
+    int perm[64] = {0};
+    for (int m = 1; m < period; m *= 2)
+        for (int i = m - 1; i >= 0; --i) {
+            const int q = perm[i];
+            perm[2 * i] = q;
+            perm[2 * i + 1] = 2 * m - 1 - q;
+        }
+    for (int i = 0; i < period; ++i) {
+        const int j = perm[i];
+        omegas[i] = 1.0 / (1.0 - rho * std::cos(pi * double(2 * j + 1) / double(2 * period)));
+    }
+    if (spectral_radius) *spectral_radius = rho;
+    clear_error();
+    return STENCIL_OK;
+}
+
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream, float* elapsed_ms) {
     if (!dst || !src || bytes <= 0 || (bytes % 16) != 0 || reps <= 0) return set_error(STENCIL_EINVAL, "bad copy args");
     hipStream_t s = as_stream(stream);

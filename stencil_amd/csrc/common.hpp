@@ -207,6 +207,13 @@ int launch_tkstrip_source(const stencil_layout& l, const void* in, void* out, co
 // the same launches on a layout that may carry halo flags (stencil_sweepk_source_halo: slab source rounds)
 int launch_tkstrip_source_halo(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
                                int64_t end, int steps, hipStream_t s);
+// kernels_strip_relax.hip: `steps` (2..4) fused relaxed source sweeps, sweep i with the weight omegas[i]
+// (host doubles, each rounded once to the grid's type): stencil_sweepk_relax's fused launches
+int launch_tkstrip_relax(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                         int64_t end, int steps, const double* omegas, hipStream_t s);
+// kernels_source.hip: one relaxed source sweep with the weight omega
+int launch_relax1(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
+                  double omega, hipStream_t s);
 // kernels_source.hip: one sweep with the source added
 int launch_source1(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
                    hipStream_t s);
@@ -215,6 +222,13 @@ int launch_source1(const stencil_layout& l, const void* in, void* out, const voi
 // (the slab's exchange-completion word, stencil_exchange_done) has reached
 // `need` (wrap-safe), or until *release != 0 (a failed job), or 10 s (then
 // it sets *release: the job reports the timeout).  A null word: no gate.
+// The per-sweep weights of a relaxed launch as the strip kernel takes them: by value, so they sit in
+// scalar registers (no device buffer, no upload).  Stage s of the launch uses w[s - 1].
+constexpr int kRelaxWeights = kSourceSteps;
+template <typename T>
+struct StripWeights {
+    T w[kRelaxWeights];
+};
 struct StripGate {
     const uint32_t* word = nullptr;
     uint32_t* release = nullptr;
@@ -237,6 +251,7 @@ struct StripExtras {
     StripGate gate;                      // signal: the halo gate (a null word: none)
     int* nsig = nullptr;                 // signal, out: the adds per face (one per tile)
     const void* src = nullptr;           // source launches (kSrc shapes): the source grid, the field's layout
+    double omega[kRelaxWeights] = {};    // relaxed launches (kRelax shapes): sweep i's weight
 };
 // The default strip shapes with at least one of the extras' options
 int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end, int steps,

@@ -5,6 +5,8 @@
 // not reproduced (CLI11 is not available to compare against).
 #include "program_options.hpp"
 
+#include <cmath>
+
 #include <cctype>
 #include <cerrno>
 #include <cstdlib>
@@ -152,6 +154,10 @@ auto ProgramOptions::parse(int argc, char** argv) -> std::optional<ProgramOption
          [&](const std::string& v) { if (v != "max" && v != "l2") return false; r.norm_l2 = v == "l2"; return true; }},
         {0, "source", Kind::Double, false, "[ext] Add X at every interior cell after each sweep (--dims 3; methods HIP, CPU).",
          [&](const std::string& v) { if (!parse_double(v, r.source)) return false; r.has_source = true; return true; }},
+        {0, "omega", Kind::Double, false, "[ext] Relax every sweep by the weight W: u + W (S(u) + g - u) (--dims 3; methods HIP, CPU).",
+         [&](const std::string& v) { if (!parse_double(v, r.omega) || !std::isfinite(r.omega)) return false; r.has_omega = true; return true; }},
+        {0, "cheby", Kind::Unsigned, false, "[ext] Relax the sweeps by a Chebyshev schedule of P weights (a power of two in 1..64; not with --omega).",
+         [&](const std::string& v) { return parse_unsigned(v, r.cheby) && r.cheby >= 1 && r.cheby <= 64 && !(r.cheby & (r.cheby - 1)); }},
     };
 
     auto find_long = [&](const std::string& n) -> Opt* {
@@ -223,6 +229,17 @@ auto ProgramOptions::parse(int argc, char** argv) -> std::optional<ProgramOption
         if (r.kernel != "auto" && r.kernel != "temporalk") return fail("--source needs --kernel auto or temporalk");
         for (const std::string& m : r.method_names)
             if (m != "HIP" && m != "CPU") return fail("--source is valid with the methods HIP and CPU only (got " + m + ")");
+    }
+    if (r.relaxed()) {
+        // the relaxed sweeps cover what --source covers (stencil_iterate_relax and the CPU loop)
+        const std::string opt = r.has_omega ? "--omega" : "--cheby";
+        if (r.has_omega && r.cheby) return fail("--omega and --cheby are mutually exclusive");
+        if (r.dims != 3) return fail(opt + " needs a 3D grid (--dims 3)");
+        if (r.box || r.radius != 1) return fail(opt + " covers the 7-point star only (--shape star, -r 1)");
+        if (r.gpus != 1) return fail(opt + " runs on one GPU (no --gpus)");
+        if (r.kernel != "auto" && r.kernel != "temporalk") return fail(opt + " needs --kernel auto or temporalk");
+        for (const std::string& m : r.method_names)
+            if (m != "HIP" && m != "CPU") return fail(opt + " is valid with the methods HIP and CPU only (got " + m + ")");
     }
     return r;
 }

@@ -47,8 +47,12 @@ struct ProgramOptions {
     bool norm_l2 = false;          // --norm max|l2: the norm of the update
     bool has_source = false;       // --source VALUE: a constant added at every interior cell after each sweep
     double source = 0.0;           //   (u' = S(u) + VALUE; --dims 3, methods HIP and CPU)
+    bool has_omega = false;        // --omega W: every sweep relaxed by W, u' = u + W (S(u) + g - u); g = 0 without --source
+    double omega = 1.0;
+    unsigned cheby = 0;            // --cheby P: the sweeps relaxed by the Chebyshev schedule of P weights (0 = off)
 
     bool until() const { return tol >= 0.0; }
+    bool relaxed() const { return has_omega || cheby != 0; }
 
     int64_t extent_x() const { return nx >= 0 ? nx : matrix_size; }
     int64_t extent_y() const { return ny >= 0 ? ny : matrix_size; }

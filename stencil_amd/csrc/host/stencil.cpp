@@ -78,6 +78,24 @@ void Stencil::init_typed(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) const
     }
 }
 
+// --omega W: the one weight; --cheby P: the Chebyshev schedule of P weights for the Dirichlet problem of the
+// grid's extents (stencil_chebyshev_weights, host only).  Sweep i of a job takes entry i % size.
+auto Stencil::relax_schedule() const -> std::vector<double> {
+    if (options.has_omega) return {options.omega};
+    if (!options.cheby) return {};
+    stencil_problem p{};
+    p.dims = options.dims;
+    p.dtype = options.fp64 ? STENCIL_F64 : STENCIL_F32;
+    p.shape = STENCIL_STAR;
+    p.radius = 1;
+    p.nx = options.extent_x();
+    p.ny = options.extent_y();
+    p.nz = options.extent_z();
+    std::vector<double> w(options.cheby);
+    check(stencil_chebyshev_weights(&p, int32_t(options.cheby), w.data(), nullptr), "stencil_chebyshev_weights");
+    return w;
+}
+
 void Stencil::initialize_matrix() {
     if (options.fp64) init_typed(matrix64, result64);
     else init_typed(matrix32, result32);
@@ -215,12 +233,14 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     check(stencil_alloc(&l, &d.b), "stencil_alloc");
     upload(d.a, matrix);
     upload(d.b, result);
-    if (options.has_source) {
-        // the constant at every interior cell (only those have meaning), zeros around them
+    const std::vector<double> sched = relax_schedule();  // --omega / --cheby (empty: none)
+    if (options.has_source || !sched.empty()) {
+        // the constant at every interior cell (only those have meaning; relaxed sweeps without --source:
+        // zero), zeros around them
         BoundaryGrid<T> g(options.dims, matrix.width(), matrix.height(), matrix.depth(), options.radius);
         for (int64_t z = 0; z < g.depth(); ++z)
             for (int64_t y = 0; y < g.height(); ++y)
-                for (int64_t x = 0; x < g.width(); ++x) g.elem_at(z, y, x) = T(options.source);
+                for (int64_t x = 0; x < g.width(); ++x) g.elem_at(z, y, x) = T(options.has_source ? options.source : 0.0);
         check(stencil_alloc(&l, &d.src), "stencil_alloc");
         check(stencil_upload(&l, d.src, g.data(), g.row_stride(), g.rows_with_boundary(), nullptr), "upload");
     }
@@ -233,8 +253,14 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
         int fin = 0;
         check(stencil_iterate(&l, d.a, d.b, 1, nullptr, &fin, nullptr), "warm-up");
         // the source job's launches (the fused ones with their schedule choices, the single sweep)
-        if (options.has_source)
+        if (options.has_source && sched.empty())
             for (uint32_t n : {7u, 2u, 1u}) check(stencil_iterate_source(&l, d.a, d.b, d.src, n, nullptr, &fin, nullptr), "warm-up");
+        // the relaxed job's launches alike
+        if (!sched.empty())
+            for (uint32_t n : {7u, 2u, 1u})
+                check(stencil_iterate_relax(&l, d.a, d.b, d.src, n, sched.data(), uint32_t(sched.size()), 0, nullptr, &fin,
+                                            nullptr),
+                      "warm-up");
         // and the per-shape z-chunk schedule choice, timed on a shape's first
         // fused launch (kernels_strip.hip pick_schedule)
         check(stencil_prepare(&l, d.a, d.b, nullptr), "warm-up");
@@ -252,7 +278,20 @@ auto Stencil::run_typed(InputMethod method, BoundaryGrid<T>& matrix, BoundaryGri
     int final_in_b = 0;
     float ms = 0.f;
     auto const start = std::chrono::steady_clock::now();
-    if (options.has_source && options.until()) {
+    if (!sched.empty() && options.until()) {
+        uint32_t done = 0;
+        int conv = 0;
+        check(stencil_iterate_until_relax(&l, d.a, d.b, d.src, options.iterations, options.check_every,
+                                          options.norm_l2 ? STENCIL_NORM_L2 : STENCIL_NORM_MAX, options.tol, sched.data(),
+                                          uint32_t(sched.size()), 0, nullptr, &done, &final_in_b, &run_norm, &conv, &ms),
+              "stencil_iterate_until_relax");
+        sweeps_done = done;
+        run_converged = conv != 0;
+    } else if (!sched.empty()) {
+        check(stencil_iterate_relax(&l, d.a, d.b, d.src, options.iterations, sched.data(), uint32_t(sched.size()), 0,
+                                    nullptr, &final_in_b, &ms),
+              "stencil_iterate_relax");
+    } else if (options.has_source && options.until()) {
         uint32_t done = 0;
         int conv = 0;
         check(stencil_iterate_until_source(&l, d.a, d.b, d.src, options.iterations, options.check_every,
@@ -326,7 +365,8 @@ auto Stencil::run(std::string_view method_name) -> std::optional<std::chrono::st
 // ...; returns true when the final grid is in b (stencil.cpp:88-92,134).
 // Naive order always (it is the reference's checker and its CPU path).
 template <class T>
-bool Stencil::naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iterations) const {
+bool Stencil::naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iterations, unsigned first) const {
+    const std::vector<double> sched = relax_schedule();
     BoundaryGrid<T>* in = &a;
     BoundaryGrid<T>* out = &b;
     const int r = int(options.radius);
@@ -342,6 +382,8 @@ bool Stencil::naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iter
     for (unsigned i = 0; i != iterations; ++i) {
         T* src = in->data();
         T* dst = out->data();
+        // --omega / --cheby: this sweep's weight, rounded once to the grid's type
+        const T w = sched.empty() ? T(1) : T(sched[(size_t(first) + i) % sched.size()]);
         for (int64_t z = 0; z < in->depth(); ++z)
             for (int64_t y = 0; y < in->height(); ++y)
                 for (int64_t x = 0; x < in->width(); ++x) {
@@ -385,7 +427,16 @@ bool Stencil::naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iter
                     }
                     const T avged = sum * avg;
                     // --source: a second rounding after the multiply's, never one fma (built with -ffp-contract=off)
-                    dst[c] = options.has_source ? avged + T(options.source) : avged;
+                    const T j = options.has_source || !sched.empty() ? avged + T(options.has_source ? options.source : 0.0) : avged;
+                    if (sched.empty()) {
+                        dst[c] = j;
+                    } else {
+                        // the relaxed update in four roundings after the multiply: the source add above, the
+                        // difference, its weighting, the sum -- never an fma
+                        const T dlt = j - src[c];
+                        const T wd = w * dlt;
+                        dst[c] = src[c] + wd;
+                    }
                 }
         std::swap(in, out);
         swapped = !swapped;
@@ -429,7 +480,7 @@ auto Stencil::run_cpu(BoundaryGrid<T>& matrix, BoundaryGrid<T>& result) -> std::
         run_norm = HUGE_VAL;
         while (sweeps_done < options.iterations) {
             const unsigned block = std::min(options.check_every, options.iterations - sweeps_done);
-            if (naive_sweeps(*cur, *old, block)) std::swap(cur, old);
+            if (naive_sweeps(*cur, *old, block, sweeps_done)) std::swap(cur, old);
             sweeps_done += block;
             run_norm = update_norm(*cur, *old);
             if (run_norm <= options.tol) {

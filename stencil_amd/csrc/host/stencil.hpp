@@ -11,6 +11,7 @@
 #include <optional>
 #include <string>
 #include <string_view>
+#include <vector>
 
 #include "grid.hpp"
 #include "program_options.hpp"
@@ -80,8 +81,11 @@ private:
     bool check_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const;
     template <class T>
     double sum_typed(const BoundaryGrid<T>& matrix, const BoundaryGrid<T>& result) const;
+    /// `first`: the job's sweep index of the first of them (--omega / --cheby: the schedule's position).
     template <class T>
-    bool naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iterations) const;
+    bool naive_sweeps(BoundaryGrid<T>& a, BoundaryGrid<T>& b, unsigned iterations, unsigned first = 0) const;
+    /// --omega / --cheby: the weights the job's sweeps cycle through (empty: plain sweeps).
+    auto relax_schedule() const -> std::vector<double>;
     template <class T>
     double update_norm(const BoundaryGrid<T>& now, const BoundaryGrid<T>& before) const;
     template <class T>

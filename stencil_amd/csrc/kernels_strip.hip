@@ -91,9 +91,10 @@
 #define TK_XRING8 0
 #endif
 
-// kernels_strip_ilp.hip, kernels_strip_probe.hip and kernels_strip_source.hip compile this file again for
-// a few instantiations of their own: the kernel and launch_st, not the host-side schedule code
-#if defined(STRIP_ILP_TU) || defined(STRIP_SOURCE_TU)
+// kernels_strip_ilp.hip, kernels_strip_probe.hip, kernels_strip_source.hip and kernels_strip_relax.hip
+// compile this file again for a few instantiations of their own: the kernel and launch_st, not the
+// host-side schedule code
+#if defined(STRIP_ILP_TU) || defined(STRIP_SOURCE_TU) || defined(STRIP_RELAX_TU)
 #define STRIP_EXTRA_TU
 #endif
 
@@ -317,6 +318,12 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // SRC + SIG (stencil_sweepk_signal_source): the ring is indexed by march step
 // and load_rhs maps the march index to its plane through zr(), as load_plane
 // does, so a down-marching chunk's stages find the planes they walk.
+// RLX (stencil_sweepk_relax; with SRC only): every stage relaxes its source sweep with a
+// weight of its own, t_s(q) = fl(c + fl(w[s-1] * fl(J - c))) at interior cells, J the source sweep's value
+// and c = t_{s-1}(q) the centre operand the stage already holds: a subtract, a multiply and an add, each
+// rounded, never an fma.  The K weights are kernel arguments (scalar registers), stage s of every launch
+// takes w[s-1]; the host fills them per launch from the job's schedule.  Ghost cells keep their value
+// through the selects, which follow the relaxation as they follow the source add.
 // SLIVER (sliver_shape() only; fast & kSliver): the last tile column stores at most
 // 16 - 2 XR = 8 columns, so one of its tiles needs 16 lanes of a region row: XR ring lanes, its
 // output columns, the ghost column x = nx, the rest unused.  A SLIVER WORKGROUP runs four such tiles
@@ -329,12 +336,12 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // indices: [0, main_tiles) are the (tiles_x - 1) x tiles_y full-width tiles, row-major;
 // main_tiles + j is sliver workgroup j.
 template <typename T, int V, int RY, int NW, int K, bool DB, int DIAG = 0, bool SIG = false, int NS = 4, bool FP = true,
-          bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false, bool SRC = false>
+          bool HL = false, bool TIER = false, bool SPLIT = false, bool UMAX = false, bool SRC = false, bool RLX = false>
 __global__ void __launch_bounds__(64 * NW)
     tkstrip_7pt(const T* __restrict__ in, T* __restrict__ out, Geom g, int zbeg, int zend, int zchunk,
                 int tiles_x, int tiles_y, int halo_lo, int halo_hi, T avg, unsigned* __restrict__ sig,
                 unsigned long long* __restrict__ fsig, const int* __restrict__ sched, int fast, int xcd_pw,
-                TierArgs tier, StripGate gate, const T* __restrict__ rhs) {
+                TierArgs tier, StripGate gate, const T* __restrict__ rhs, StripWeights<T> rw) {
     using Tl = StripTile<T, V, RY, NW, K, DB, SPLIT>;
     using VT = typename VecS<T, V>::type;
     constexpr int XR = Tl::XR, TX = Tl::TX, TY = Tl::TY, RH = Tl::RH, RW = Tl::RW, NB = Tl::NB;
@@ -345,6 +352,8 @@ __global__ void __launch_bounds__(64 * NW)
     static_assert(!SRC || (!TIER && !UMAX && !HL && !SPLIT && DIAG == 0 && NS == 4 && !TK_SST && !TK_XRING8 &&
                            !TK_PROBE_NOBAR),
                   "SRC: plain or face-signalled launches of the source shapes only");
+    static_assert(!RLX || (SRC && !SIG && !UMAX && !TIER && !HL && !SPLIT && DIAG == 0 && K <= kRelaxWeights),
+                  "RLX: plain launches of the source shapes only");
     constexpr bool SST = Tl::SSTS && !SIG && !TIER && !HL;
     constexpr int NI = (RY + 1) / 2;  // SST: row pairs per strip
     typedef T V4T __attribute__((ext_vector_type(4)));
@@ -769,6 +778,11 @@ __global__ void __launch_bounds__(64 * NW)
                     sum += REV ? zm : zp;
                     o = DIAG == 2 ? c : __builtin_elementwise_fma(sum, (VT)(avg), VT{});
                     if constexpr (SRC) o += vr[(S - s + 2 * NR) % NR][k];  // the second rounding
+                    if constexpr (RLX) {  // three more roundings: the difference, its weighting, the sum
+                        const VT d = o - c;
+                        const VT wd = (VT)(rw.w[s - 1]) * d;
+                        o = c + wd;
+                    }
 #pragma unroll
                     for (int j = 0; j < V; ++j) {
                         if (s < K && !FAST) o[j] = (zin[s - 1] && yin[k] && xin[j]) ? o[j] : c[j];
@@ -786,6 +800,11 @@ __global__ void __launch_bounds__(64 * NW)
                     sum += REV ? zm[j] : zp[j];
                     o[j] = DIAG == 2 ? c[j] : sfma0(sum, avg);
                     if constexpr (SRC) o[j] += vr[(S - s + 2 * NR) % NR][k][j];  // the second rounding
+                    if constexpr (RLX) {  // three more roundings: the difference, its weighting, the sum
+                        const T d = o[j] - c[j];
+                        const T wd = rw.w[s - 1] * d;
+                        o[j] = c[j] + wd;
+                    }
                     if (s < K && !FAST) o[j] = (zin[s - 1] && yin[k] && xin[j]) ? o[j] : c[j];
                     // TIER producer: t_K keeps the ghost cells too (they go to the slots)
                     if (PROD && s == K && !FAST) o[j] = (yin[k] && xin[j]) ? o[j] : c[j];
@@ -1018,20 +1037,21 @@ enum : unsigned {
     kSplit = 16,    // SPLIT: two strips per wave
     kUmax = 32,     // UMAX: the launch reports its update maximum
     kSrc = 64,      // SRC: every sweep adds the source grid (StripExtras::src)
+    kRelax = 128,   // RLX: every sweep is relaxed by its own weight (StripExtras::omega); with kSrc only
 };
 template <typename T_, int V_, int RY_, int NW_, int K_, unsigned OPT = 0, int NS_ = 4, int DIAG_ = 0>
 struct Shape {
     using T = T_;
     static constexpr int V = V_, RY = RY_, NW = NW_, K = K_, NS = NS_, DIAG = DIAG_;
     static constexpr bool DB = !(OPT & kOneBuf), SIG = OPT & kSig, FP = !(OPT & kNoFast), HL = OPT & kHistLds,
-                          SPLIT = OPT & kSplit, UMAX = OPT & kUmax, SRC = OPT & kSrc;
+                          SPLIT = OPT & kSplit, UMAX = OPT & kUmax, SRC = OPT & kSrc, RLX = OPT & kRelax;
     using Tile = StripTile<T, V, RY, NW, K, DB, SPLIT>;
 };
 // The one place that maps a shape onto the kernel's positional parameters.
 template <class S, bool TIER = false>
 auto strip_kernel() {
     return tkstrip_7pt<typename S::T, S::V, S::RY, S::NW, S::K, S::DB, S::DIAG, S::SIG, S::NS, S::FP, S::HL, TIER,
-                       S::SPLIT, S::UMAX, S::SRC>;
+                       S::SPLIT, S::UMAX, S::SRC, S::RLX>;
 }
 
 // The default shapes (8 waves each): cells per lane and rows per strip by
@@ -1277,6 +1297,9 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
     StripGate gate = SIG ? x.gate : StripGate{};
     unsigned long long* fsig = SIG ? x.fsig : nullptr;
     if (S::UMAX) (SIG ? gate.umax : fsig) = x.umax;
+    StripWeights<T> rw{};  // RLX: stage s takes w[s - 1], each the double rounded once to T
+    if (S::RLX)
+        for (int i = 0; i < K && i < kRelaxWeights; ++i) rw.w[i] = T(x.omega[i]);
     auto launch = [&](bool packed) {
         // the sliver table's trial: its other side is the plain launch (whose own first call settles its
         // own trial inside; pick_schedule keeps each side's best of three)
@@ -1286,7 +1309,7 @@ int launch_st(const stencil_layout& l, const void* in, void* out, int64_t begin,
                            static_cast<const T*>(in), static_cast<T*>(out), g, int(begin), int(end), zc, int(gx),
                            int(gy), int(lo), int(hi), avg_weight<T>(l.prob), SIG ? x.sig : nullptr, fsig,
                            packed ? sched : nullptr, fast_of(packed), packed ? 0 : xcd_pw, TierArgs{}, gate,
-                           S::SRC ? static_cast<const T*>(x.src) : nullptr);
+                           S::SRC ? static_cast<const T*>(x.src) : nullptr, rw);
         return hipGetLastError();
     };
     if (sched && verdict && verdict->load() == kPackUntested) return pick_schedule(verdict, s, launch);
@@ -1401,7 +1424,7 @@ int tier_launch(const stencil_layout& l, const void* in, void* out, TierJob* j, 
     hipLaunchKernelGGL(kern, dim3(unsigned(2 * j->tiles)), dim3(64, 8, 1), 0, s, static_cast<const double*>(in),
                        static_cast<double*>(out), g, 0, int(g.nz), 0, int(gx), int(gy), 0, 0,
                        avg_weight<double>(l.prob), nullptr, nullptr, nullptr, fast, 0, j->a, StripGate{},
-                       static_cast<const double*>(nullptr));
+                       static_cast<const double*>(nullptr), StripWeights<double>{});
     STENCIL_LAUNCH_CHECK();
     j->a.base += uint32_t(g.nz + 1);  // the flags end at base + nz + 1: the next launch's origin
     return STENCIL_OK;
@@ -1523,6 +1546,42 @@ int launch_tkstrip_source_signal(const stencil_layout& l, const void* in, void* 
         return f32 ? launch_st<SourceSignalShape<float, 4>>(l, in, out, begin, end, s, x)
                    : launch_st<SourceSignalShape<double, 4>>(l, in, out, begin, end, s, x);
     default: return set_error(STENCIL_EINVAL, "face-signalled source sweeps: steps must be 3 or 4 (got %d)", steps);
+    }
+}
+#elif defined(STRIP_RELAX_TU)
+// kernels_strip_relax.hip: the relaxed source launches (RLX above the kernel).  The
+// relaxation adds no ring and no load, only the K weights in scalar registers and three operations per cell
+// and stage, but the stage's centre operand now lives until the stage's last operation.  Rows per strip by
+// [fp64][K - 2]: the largest count, not above the plain source shape's (7 / 6 / 5), that compiles without
+// scratch (DESIGN.md §5.8 has the table).  TK_RELAX_ROWS: the compile-time probe of that choice.  No shape
+// may use scratch.
+#ifndef TK_RELAX_ROWS
+#define TK_RELAX_ROWS {{7, 6, 5}, {7, 6, 4}}
+#endif
+constexpr int kRelaxRows[2][3] = TK_RELAX_ROWS;
+template <typename T, int K>
+using RelaxShape = Shape<T, sizeof(T) == 8 ? 1 : 2, kRelaxRows[sizeof(T) == 8][K - 2], 8, K, kSrc | kRelax>;
+
+int launch_tkstrip_relax(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                         int64_t end, int steps, const double* omegas, hipStream_t s) {
+    if (!temporal2_supports(l.prob) || (l.prob.flags & (STENCIL_HALO_LO | STENCIL_HALO_HI)))
+        return set_error(STENCIL_EUNSUPPORTED, "relaxed sweeps cover the 3D r=1 naive 7-point star without halo flags");
+    if (steps < 2 || steps > kRelaxWeights)
+        return set_error(STENCIL_EINVAL, "fused relaxed sweeps: steps must be 2..%d (got %d)", kRelaxWeights, steps);
+    StripExtras x;
+    x.src = src;
+    for (int i = 0; i < steps; ++i) x.omega[i] = omegas[i];
+    const bool f32 = l.prob.dtype == STENCIL_F32;
+    switch (steps) {
+    case 2:
+        return f32 ? launch_st<RelaxShape<float, 2>>(l, in, out, begin, end, s, x)
+                   : launch_st<RelaxShape<double, 2>>(l, in, out, begin, end, s, x);
+    case 3:
+        return f32 ? launch_st<RelaxShape<float, 3>>(l, in, out, begin, end, s, x)
+                   : launch_st<RelaxShape<double, 3>>(l, in, out, begin, end, s, x);
+    default:
+        return f32 ? launch_st<RelaxShape<float, 4>>(l, in, out, begin, end, s, x)
+                   : launch_st<RelaxShape<double, 4>>(l, in, out, begin, end, s, x);
     }
 }
 #else
@@ -2031,7 +2090,7 @@ int launch_tkstrip_default(const stencil_layout& l, const void* in, void* out, i
                 : launch_default<kSig>(l, in, out, begin, end, steps, s, x, what);
 }
 
-#endif  // STRIP_ILP_TU / STRIP_SOURCE_TU
+#endif  // STRIP_ILP_TU / STRIP_SOURCE_TU / STRIP_RELAX_TU
 
 }  // namespace stencil
 

@@ -487,6 +487,61 @@ class JacobiEngine:
                                                 ctypes.byref(steps)), "stencil_source_plan", lib=self.lib)
         return {"launches": int(launches.value), "steps": int(steps.value)}
 
+    # ------------------------------------------------------ relaxed sweeps
+    # u' = u + w (S(u) + g - u) with a weight per sweep (stencil_*_relax): damped Jacobi with one weight,
+    # Chebyshev / scheduled-relaxation Jacobi with chebyshev_weights()'s schedule.  The grid g is set_source()'s
+    # (a grid of zeros for a plain smoother).
+    @staticmethod
+    def _weights(omegas):
+        w = [float(x) for x in (omegas if hasattr(omegas, "__len__") else [omegas])]
+        return (ctypes.c_double * len(w))(*w), len(w)
+
+    def sweepk_relax(self, src_grid: torch.Tensor, dst_grid: torch.Tensor, begin: int, end: int, omegas,
+                     stream=None) -> None:
+        """dst = len(omegas) relaxed sweeps of src over [begin, end) in one
+        launch (stencil_sweepk_relax; 1..4 weights, sweep i takes omegas[i])."""
+        w, n = self._weights(omegas)
+        _lib.check(self.lib.stencil_sweepk_relax(ctypes.byref(self.layout), ctypes.c_void_p(src_grid.data_ptr()),
+                                                 ctypes.c_void_p(dst_grid.data_ptr()), self._source_ptr(), begin, end, n,
+                                                 w if n else None, _stream_handle(stream)),
+                   "stencil_sweepk_relax", lib=self.lib)
+
+    def iterate_relax(self, iterations: int, omegas, phase: int = 0, stream=None, timed: bool = False):
+        """iterate_source() with sweep i relaxed by omegas[(phase + i) %
+        len(omegas)] (stencil_iterate_relax; one number: a constant weight);
+        returns (final grid tensor, device ms or None)."""
+        w, n = self._weights(omegas)
+        fin, ms = ctypes.c_int(0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_iterate_relax(ctypes.byref(self.layout), ctypes.c_void_p(self.a.data_ptr()),
+                                                  ctypes.c_void_p(self.b.data_ptr()), self._source_ptr(), iterations,
+                                                  w if n else None, n, phase, _stream_handle(stream), ctypes.byref(fin),
+                                                  ctypes.byref(ms) if timed else None),
+                   "stencil_iterate_relax", lib=self.lib)
+        return (self.b if fin.value else self.a), (ms.value if timed else None)
+
+    def iterate_until_relax(self, tol: float, max_iterations: int, omegas, check_every: int = 100, norm: str = "max",
+                            phase: int = 0, stream=None, timed: bool = False) -> "UntilResult":
+        """iterate_until_source() on relaxed sweeps (stencil_iterate_until_relax);
+        make check_every a multiple of len(omegas)."""
+        w, n = self._weights(omegas)
+        done, fin, conv = ctypes.c_uint32(0), ctypes.c_int(0), ctypes.c_int(0)
+        last, ms = ctypes.c_double(0.0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_iterate_until_relax(
+            ctypes.byref(self.layout), ctypes.c_void_p(self.a.data_ptr()), ctypes.c_void_p(self.b.data_ptr()),
+            self._source_ptr(), max_iterations, check_every, _lib.NORM_NAMES[norm], tol, w if n else None, n, phase,
+            _stream_handle(stream), ctypes.byref(done), ctypes.byref(fin), ctypes.byref(last), ctypes.byref(conv),
+            ctypes.byref(ms) if timed else None), "stencil_iterate_until_relax", lib=self.lib)
+        return UntilResult(self.b if fin.value else self.a, int(done.value), bool(conv.value), float(last.value),
+                           ms.value if timed else None)
+
+    def relax_plan(self, iterations: int) -> dict:
+        """iterate_relax(iterations) as kernel launches, and the sweeps its
+        fused launch takes (stencil_relax_plan, host only)."""
+        launches, steps = ctypes.c_int64(0), ctypes.c_int32(0)
+        _lib.check(self.lib.stencil_relax_plan(ctypes.byref(self.layout), iterations, ctypes.byref(launches),
+                                               ctypes.byref(steps)), "stencil_relax_plan", lib=self.lib)
+        return {"launches": int(launches.value), "steps": int(steps.value)}
+
 
 @dataclass(frozen=True)
 class UntilResult:
@@ -868,3 +923,14 @@ def slab_source_plan(spec: StencilSpec, nx: int, ny: int, nz: int, iterations: i
     _lib.check(lib.stencil_slab_source_plan(ctypes.byref(prob), iterations, ctypes.byref(rounds), ctypes.byref(steps)),
                "stencil_slab_source_plan", lib=lib)
     return {"rounds": int(rounds.value), "steps": int(steps.value)}
+
+
+def chebyshev_weights(spec: StencilSpec, nx: int, ny: int, nz: int, period: int, lib=None) -> list:
+    """stencil_chebyshev_weights for the Dirichlet problem of these extents
+    (host only, no device needed): the `period` weights (a power of two in
+    1..64) in the Lebedev-Finogenov order, for iterate_relax / iterate_until_relax."""
+    lib = lib if lib is not None else _lib.load()
+    prob = spec.problem(nx, ny, nz)
+    w = (ctypes.c_double * max(1, int(period)))()
+    _lib.check(lib.stencil_chebyshev_weights(ctypes.byref(prob), period, w, None), "stencil_chebyshev_weights", lib=lib)
+    return [float(x) for x in w[:period]]
