@@ -39,8 +39,10 @@ HOST_HDRS := $(wildcard stencil_amd/csrc/host/*.hpp)
 FAKE := tests/cpu_slab/libslab_fake.so
 # the same fake device with a source sweep: slab_core.hpp's source rounds (tests/cpu_slab_source/)
 FAKE_SRC := tests/cpu_slab_source/libslab_fake_source.so
+# and with a relaxed sweep on top: slab_core.hpp's relaxed rounds (tests/cpu_slab_relax/)
+FAKE_RLX := tests/cpu_slab_relax/libslab_fake_relax.so
 
-all: $(LIB) $(LIB_DBG) $(CLI) oracle $(FAKE) $(FAKE_SRC)
+all: $(LIB) $(LIB_DBG) $(CLI) oracle $(FAKE) $(FAKE_SRC) $(FAKE_RLX)
 
 $(OBJ)/%.o: stencil_amd/csrc/%.hip $(wildcard stencil_amd/csrc/*.hpp) include/stencil_hip.h
 	@mkdir -p $(OBJ)
@@ -107,8 +109,13 @@ $(FAKE_SRC): tests/cpu_slab_source/fake_source.cpp tests/cpu_slab/fake_dev.cpp s
 	$(CXX) $(CXXFLAGS) -fPIC -shared -pthread -Istencil_amd/csrc -Ioracle -o $@ $< -Loracle -loracle \
 	    -Wl,-rpath,'$$ORIGIN/../../oracle'
 
+$(FAKE_RLX): tests/cpu_slab_relax/fake_relax.cpp tests/cpu_slab_source/fake_source.cpp tests/cpu_slab/fake_dev.cpp \
+             stencil_amd/csrc/slab_core.hpp stencil_amd/csrc/errors.hpp include/stencil_hip.h oracle/liboracle.so
+	$(CXX) $(CXXFLAGS) -fPIC -shared -pthread -Istencil_amd/csrc -Ioracle -o $@ $< -Loracle -loracle \
+	    -Wl,-rpath,'$$ORIGIN/../../oracle'
+
 clean:
-	rm -rf build $(LIB) $(LIB_DBG) $(FAKE) $(FAKE_SRC)
+	rm -rf build $(LIB) $(LIB_DBG) $(FAKE) $(FAKE_SRC) $(FAKE_RLX)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -88,7 +88,9 @@ int stencil_last_error(void);
  * workgroups on the exchange-completion word: stencil_slab_round_info),
  * STENCIL_SLAB_SOURCE_SIGNAL=0 (the full source rounds of a face-signalled
  * slab job, stencil_slab_run_source, take the boundary + interior form instead
- * of one face-signalled source launch: stencil_slab_source_round_form),
+ * of one face-signalled source launch: stencil_slab_source_round_form; the
+ * same knob governs the relaxed rounds, stencil_slab_run_relax:
+ * stencil_slab_relax_round_form),
  * STENCIL_UNTIL_FUSED=0 (stencil_iterate_until checks every block with a
  * single sweep and stencil_diff_norms' kernels instead of the checking K-step
  * launch, stencil_sweepk_update_max: the A/B lever and the fallback). */
@@ -615,6 +617,38 @@ int stencil_relax_plan(const stencil_layout* l, uint32_t iterations, int64_t* la
 int stencil_chebyshev_weights(const stencil_problem* p, int32_t period, double* omegas,
                               double* spectral_radius);
 
+/* Relaxed launches on slab layouts (the launches of stencil_slab_run_relax).
+ * stencil_sweepk_relax_halo is stencil_sweepk_relax for layouts that may carry
+ * STENCIL_HALO_LO / STENCIL_HALO_HI, exactly as stencil_sweepk_source_halo is
+ * to stencil_sweepk_source: with flags it needs halo >= steps, with flags == 0
+ * it is bitwise stencil_sweepk_relax (which itself keeps refusing halo flags).
+ * On a halo side stage s of K = steps is computed for planes
+ * [-(K - s), nz + K - s); each advanced halo cell takes `src` of its own plane
+ * and the stage's weight, omegas[s - 1] rounded once to the grid's type.  The
+ * reads of `src` are those documented for stencil_sweepk_source_halo.  It
+ * stores the interior cells of [begin, end) of `out` and nothing else.
+ * steps = 1 reads the halo planes of `in` and advances none.
+ *   stencil_sweepk_signal_relax / _gated: stencil_sweepk_signal_source /
+ * _gated with the weights (steps 3 or 4): `out` is bitwise
+ * stencil_sweepk_relax_halo's; the counters, the face signal and the halo gate
+ * are exactly stencil_sweepk_signal_source's.  Stage s applies omegas[s - 1]
+ * whichever way a chunk is marched.  The rows per strip are the signalled
+ * source launch's (6 at K = 3, 4 at K = 4), so *signals_per_face equals that
+ * launch's.
+ * STENCIL_EINVAL: as stencil_sweepk_source_halo / stencil_sweepk_signal_source
+ * (in their order), then NULL omegas or a weight that is NaN or infinite.
+ * STENCIL_EUNSUPPORTED: as stencil_sweepk_source_halo. */
+int stencil_sweepk_relax_halo(const stencil_layout* l, const void* in, void* out, const void* src,
+                              int64_t begin, int64_t end, int32_t steps, const double* omegas, void* stream);
+int stencil_sweepk_signal_relax(const stencil_layout* l, const void* in, void* out, const void* src,
+                                int64_t begin, int64_t end, int32_t steps, const double* omegas,
+                                uint32_t* counters, uint64_t* face_signal, int32_t* signals_per_face,
+                                void* stream);
+int stencil_sweepk_signal_relax_gated(const stencil_layout* l, const void* in, void* out, const void* src,
+                                      int64_t begin, int64_t end, int32_t steps, const double* omegas,
+                                      uint32_t* counters, uint64_t* face_signal, uint32_t gate_need,
+                                      uint32_t* release_flag, int32_t* signals_per_face, void* stream);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,
@@ -783,6 +817,55 @@ int stencil_slab_run_until_source(stencil_slab_job* job, uint32_t max_iterations
                                   int* converged, float* elapsed_ms);
 int stencil_slab_source_plan(const stencil_problem* global, uint32_t iterations, int64_t* rounds, int32_t* steps);
 int stencil_slab_source_round_form(const stencil_slab_job* job, int32_t* form);
+/* Relaxed sweeps in slab jobs: u' = u + w (S(u) + g - u) with a weight per
+ * sweep (damped Jacobi; Chebyshev Jacobi with a schedule) across the slabs.
+ * Scope: that of the source rounds -- two-grid jobs of the 3D 7-point star,
+ * r = 1, naive order, kernel AUTO or TEMPORALK, fp32 / fp64, slab mode (slabs
+ * may share a GPU) and rank mode, STENCIL_SLAB_PERIODIC allowed.  The grid g is
+ * stencil_slab_set_source's; for a plain smoother it is a grid of zeros.
+ *   stencil_slab_run_relax: stencil_slab_run_source with weights.  `omegas` is
+ * a host array of `period` doubles; sweep i of the call (0-based) takes
+ * omegas[(phase + i) % period], so a caller continues a schedule across calls
+ * by passing the sweeps done so far as `phase`.  Rounds take
+ * Ks = min(K, STENCIL_SOURCE_MAX_STEPS) sweeps, the remainder as one shorter
+ * round; the halo depth stays K; all slabs of a round take the same weights,
+ * which travel as launch arguments (nothing is uploaded per round).  Results
+ * are bitwise those of stencil_iterate_relax on one grid, and it alternates
+ * freely with stencil_slab_run and stencil_slab_run_source.  The form of a
+ * full relaxed round follows the source round's rule: one
+ * stencil_sweepk_signal_relax launch per slab where the job's rounds are
+ * face-signalled, Ks = K >= 3, the job does not wait for its faces in the
+ * command processor (STENCIL_SLAB_CPWAIT=1) and STENCIL_SLAB_SOURCE_SIGNAL is
+ * not 0 -- the one knob governs source and relaxed rounds alike -- gated when
+ * the job is and the relaxed launch's own tiles meet the gate's rule (decided
+ * once per job, apart from the source rounds' decision).  Every other round --
+ * staged jobs', remainders, Ks < K (K = 5 jobs), slabs sharing a GPU -- is
+ * boundary + interior launches of stencil_sweepk_relax_halo, or one launch
+ * with STENCIL_SLAB_SERIAL=1.  stencil_slab_relax_round_form reports a full
+ * relaxed round's form (STENCIL_SLAB_FORM_SIGNALLED, _BOUNDARY_INTERIOR or
+ * _SERIAL).
+ *   stencil_slab_run_until_relax: stencil_slab_run_until's arguments, stopping
+ * rule and edge cases on relaxed rounds, always with the un-fused check:
+ * block - 1 relaxed sweeps as run_relax issues them, one round of a single
+ * relaxed sweep, then stencil_diff_norms' kernels per slab.  The schedule
+ * index runs on across blocks and the checking sweep takes its own weight.
+ * Counts, norms (bit for bit) and grid equal stencil_iterate_until_relax's on
+ * one grid.
+ *   stencil_slab_relax_plan (host only) equals stencil_slab_source_plan.
+ * STENCIL_EINVAL: a NULL job or omegas, period == 0, a weight that is NaN or
+ * infinite, run*_relax before stencil_slab_set_source (the message names
+ * set_source), run_until's argument errors.  STENCIL_EUNSUPPORTED (the message
+ * names the restriction): STENCIL_SLAB_ROLLING jobs, anything but the 3D r = 1
+ * naive 7-point star; run_until_relax in rank mode.  A refused call leaves the
+ * job usable.  Every host wait goes through the job's deadline. */
+int stencil_slab_run_relax(stencil_slab_job* job, uint32_t iterations, const double* omegas, uint32_t period,
+                           uint32_t phase, float* elapsed_ms);
+int stencil_slab_run_until_relax(stencil_slab_job* job, uint32_t max_iterations, uint32_t check_every,
+                                 int32_t norm, double tol, const double* omegas, uint32_t period,
+                                 uint32_t phase, uint32_t* iterations_done, double* last_norm, int* converged,
+                                 float* elapsed_ms);
+int stencil_slab_relax_plan(const stencil_problem* global, uint32_t iterations, int64_t* rounds, int32_t* steps);
+int stencil_slab_relax_round_form(const stencil_slab_job* job, int32_t* form);
 /* Per-plane interior sums of the current global grid (nz doubles, host). */
 int stencil_slab_plane_sums(stencil_slab_job* job, double* sums);
 /* Kernel timing for roofline figures: with timing on, every round records

@@ -70,6 +70,9 @@ EXPORTED_SYMBOLS = (
     "stencil_slab_source_plan", "stencil_slab_source_round_form",
     "stencil_sweepk_relax", "stencil_iterate_relax", "stencil_iterate_until_relax", "stencil_relax_plan",
     "stencil_chebyshev_weights",
+    "stencil_sweepk_relax_halo", "stencil_sweepk_signal_relax", "stencil_sweepk_signal_relax_gated",
+    "stencil_slab_run_relax", "stencil_slab_run_until_relax", "stencil_slab_relax_plan",
+    "stencil_slab_relax_round_form",
 )
 
 
@@ -125,7 +128,8 @@ def load(debug: bool | None = None) -> ctypes.CDLL:
             f"{path} is missing: the HIP extension has not been built "
             "(run `make` or `python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in {**signatures(), **slab_until_signatures(), **slab_source_signatures()}.items():
+    for name, (res, args) in {**signatures(), **slab_until_signatures(), **slab_source_signatures(),
+                              **slab_relax_signatures()}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -206,6 +210,13 @@ def signatures() -> dict:
         "stencil_sweepk_signal_source_gated": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
                                                        c_void_p, c_void_p, c_uint32, c_void_p, POINTER(c_int32),
                                                        c_void_p]),
+        "stencil_sweepk_relax_halo": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                              POINTER(c_double), c_void_p]),
+        "stencil_sweepk_signal_relax": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                                POINTER(c_double), c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+        "stencil_sweepk_signal_relax_gated": (c_int, [L, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                                      POINTER(c_double), c_void_p, c_void_p, c_uint32, c_void_p,
+                                                      POINTER(c_int32), c_void_p]),
         "stencil_sweepk_geometry": (c_int, [L, c_int64, c_int64, c_int32, POINTER(c_int64), POINTER(c_int32),
                                             POINTER(c_int32)]),
         "stencil_sweepk_signal": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
@@ -277,6 +288,21 @@ def slab_source_signatures() -> dict:
                                                   POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
         "stencil_slab_source_plan": (c_int, [POINTER(Problem), c_uint32, POINTER(c_int64), POINTER(c_int32)]),
         "stencil_slab_source_round_form": (c_int, [c_void_p, POINTER(c_int32)]),
+    }
+
+
+def slab_relax_signatures() -> dict:
+    """The slab jobs' relaxed-sweep entry points.  Kept apart from the others
+    for the reason slab_source_signatures() gives: only tests/cpu_slab_relax/
+    binds them to a fake device of its own."""
+    return {
+        "stencil_slab_run_relax": (c_int, [c_void_p, c_uint32, POINTER(c_double), c_uint32, c_uint32,
+                                           POINTER(c_float)]),
+        "stencil_slab_run_until_relax": (c_int, [c_void_p, c_uint32, c_uint32, c_int32, c_double, POINTER(c_double),
+                                                 c_uint32, c_uint32, POINTER(c_uint32), POINTER(c_double),
+                                                 POINTER(c_int), POINTER(c_float)]),
+        "stencil_slab_relax_plan": (c_int, [POINTER(Problem), c_uint32, POINTER(c_int64), POINTER(c_int32)]),
+        "stencil_slab_relax_round_form": (c_int, [c_void_p, POINTER(c_int32)]),
     }
 
 

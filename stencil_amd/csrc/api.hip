@@ -357,6 +357,25 @@ int source_signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_
     *slots = info.slots;
     return STENCIL_OK;
 }
+int relax_signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, int steps, int64_t* tiles,
+                                 int64_t* workgroups, int* slots) {
+    LaunchInfo info;
+    tl_dry_launch = &info;
+    int nsig = 0;
+    void* fake = reinterpret_cast<void*>(uintptr_t(1));  // never touched in a dry launch
+    StripExtras x;
+    x.signal = true;
+    x.nsig = &nsig;
+    x.src = fake;
+    const int rc = launch_tkstrip_relax_signal(l, nullptr, fake, begin, end, steps, x, nullptr);
+    tl_dry_launch = nullptr;
+    if (rc != STENCIL_OK) return rc;
+    if (info.steps == 0) return set_error(STENCIL_EUNSUPPORTED, "no face-signalled relaxed launch was described");
+    *tiles = nsig;
+    *workgroups = info.workgroups;
+    *slots = info.slots;
+    return STENCIL_OK;
+}
 }  // namespace stencil
 
 extern "C" {
@@ -1652,6 +1671,65 @@ int stencil_sweepk_relax(const stencil_layout* l, const void* in, void* out, con
 
 int stencil_relax_plan(const stencil_layout* l, uint32_t iterations, int64_t* launches, int32_t* steps) {
     return stencil_source_plan(l, iterations, launches, steps);
+}
+
+// Relaxed launches on slab layouts (the launches of stencil_slab_run_relax): source_halo_args' checks in their
+// order, then the steps, then the weights.
+int stencil_sweepk_relax_halo(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                              int64_t end, int32_t steps, const double* omegas, void* stream) {
+    if (int rc = source_halo_args(l, in, out, src, begin, end)) return rc;
+    if (steps < 1 || steps > kSourceSteps)
+        return set_error(STENCIL_EINVAL, "steps must be 1..%d (got %d)", kSourceSteps, steps);
+    if (int rc = check_schedule(omegas, uint32_t(steps))) return rc;
+    // (a halo side needs halo >= steps: the strip launch checks it, as stencil_sweepk's does)
+    const int rc = steps == 1 ? launch_relax1(*l, in, out, src, begin, end, omegas[0], as_stream(stream))
+                              : launch_tkstrip_relax_halo(*l, in, out, src, begin, end, steps, omegas, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+static int sweepk_signal_relax(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                               int64_t end, int32_t steps, const double* omegas, const SweepkExtras& e, void* stream) {
+    if (int rc = source_halo_args(l, in, out, src, begin, end)) return rc;
+    if (steps < 3 || steps > kSourceSteps)
+        return set_error(STENCIL_EINVAL, "face-signalled relaxed sweeps: steps must be 3..%d (got %d)", kSourceSteps, steps);
+    if (!e.counters) return set_error(STENCIL_EINVAL, "null counters");
+    // a range shorter than `steps` planes would signal one face only
+    if (end - begin < steps)
+        return set_error(STENCIL_EINVAL, "a face-signalled range needs at least %d planes (got %lld)", steps,
+                         (long long)(end - begin));
+    if (int rc = check_schedule(omegas, uint32_t(steps))) return rc;
+    int nsig = 0;
+    StripExtras x;
+    x.signal = true;
+    x.sig = e.counters;
+    x.fsig = reinterpret_cast<unsigned long long*>(e.face_signal);
+    x.nsig = &nsig;
+    x.src = src;
+    for (int i = 0; i < steps; ++i) x.omega[i] = omegas[i];
+    if (e.gated) {
+        x.gate.word = e.counters + 3;
+        x.gate.release = e.release_flag;
+        x.gate.need = e.gate_need;
+    }
+    return sweepk_done(launch_tkstrip_relax_signal(*l, in, out, begin, end, steps, x, as_stream(stream)), nsig,
+                       e.signals_per_face);
+}
+
+int stencil_sweepk_signal_relax(const stencil_layout* l, const void* in, void* out, const void* src, int64_t begin,
+                                int64_t end, int32_t steps, const double* omegas, uint32_t* counters,
+                                uint64_t* face_signal, int32_t* signals_per_face, void* stream) {
+    return sweepk_signal_relax(l, in, out, src, begin, end, steps, omegas,
+                               SweepkExtras{}.signalling(counters, face_signal, signals_per_face), stream);
+}
+
+int stencil_sweepk_signal_relax_gated(const stencil_layout* l, const void* in, void* out, const void* src,
+                                      int64_t begin, int64_t end, int32_t steps, const double* omegas,
+                                      uint32_t* counters, uint64_t* face_signal, uint32_t gate_need,
+                                      uint32_t* release_flag, int32_t* signals_per_face, void* stream) {
+    return sweepk_signal_relax(
+        l, in, out, src, begin, end, steps, omegas,
+        SweepkExtras{}.signalling(counters, face_signal, signals_per_face).gate(gate_need, release_flag), stream);
 }
 
 int stencil_iterate_relax(const stencil_layout* l, void* a, void* b, const void* src, uint32_t iterations,

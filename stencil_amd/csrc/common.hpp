@@ -211,6 +211,9 @@ int launch_tkstrip_source_halo(const stencil_layout& l, const void* in, void* ou
 // (host doubles, each rounded once to the grid's type): stencil_sweepk_relax's fused launches
 int launch_tkstrip_relax(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
                          int64_t end, int steps, const double* omegas, hipStream_t s);
+// the same launches on a layout that may carry halo flags (stencil_sweepk_relax_halo: slab relaxed rounds)
+int launch_tkstrip_relax_halo(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                              int64_t end, int steps, const double* omegas, hipStream_t s);
 // kernels_source.hip: one relaxed source sweep with the weight omega
 int launch_relax1(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin, int64_t end,
                   double omega, hipStream_t s);
@@ -262,6 +265,14 @@ int launch_tkstrip_source_signal(const stencil_layout& l, const void* in, void* 
 // api.hip: the tiles (adds per face), workgroups and resident slots of that launch over [begin, end), by a dry launch
 int source_signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, int steps, int64_t* tiles,
                                   int64_t* workgroups, int* slots);
+// kernels_strip_relax.hip: the face-signalled relaxed launch (steps 3 or 4; x.omega, x.src, x.sig and, gated,
+// x.gate)
+int launch_tkstrip_relax_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
+                                int steps, const StripExtras& x, hipStream_t s);
+// api.hip: that launch's tiles, workgroups and resident slots, by a dry launch.  A query of its own: the
+// launch's rows per strip come from its own table (TK_RELAXSIG_ROWS), not from the signalled source launch's
+int relax_signal_launch_geometry(const stencil_layout& l, int64_t begin, int64_t end, int steps, int64_t* tiles,
+                                 int64_t* workgroups, int* slots);
 // stencil_iterate_until's rule (api.hip): the sweeps of the checking K-step launch that ends a block of
 // `block` sweeps on problem `p`, or 0 when the block keeps the un-fused check
 int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm);

@@ -46,8 +46,9 @@ __global__ void __launch_bounds__(kSX * kSY)
     }
 }
 
-// The relaxed sibling (stencil_sweepk_relax with steps = 1, a relaxed job's remainder of one, the sweep before
-// stencil_iterate_until_relax's check): the same march and the same value J, then
+// The relaxed sibling (stencil_sweepk_relax and, on slab layouts, stencil_sweepk_relax_halo with steps = 1: a
+// relaxed job's remainder of one, the sweep before stencil_iterate_until_relax's and stencil_slab_run_until_relax's
+// check; a single sweep reads a halo side's planes of `in` and advances none): the same march and the same value J, then
 // out(c) = fl(in(c) + fl(w * fl(J - in(c)))) -- the subtract, the multiply and the add each rounded.
 template <typename T>
 __global__ void __launch_bounds__(kSX * kSY)

@@ -323,7 +323,11 @@ __device__ __forceinline__ void sc1_store(void* p, const VT& v) {
 // and c = t_{s-1}(q) the centre operand the stage already holds: a subtract, a multiply and an add, each
 // rounded, never an fma.  The K weights are kernel arguments (scalar registers), stage s of every launch
 // takes w[s-1]; the host fills them per launch from the job's schedule.  Ghost cells keep their value
-// through the selects, which follow the relaxation as they follow the source add.
+// through the selects, which follow the relaxation as they follow the source add.  The relaxation sits
+// before those selects, so a halo side's advanced planes (stencil_sweepk_relax_halo) are relaxed like the
+// slab's own: stage s weighs planes [-(K - s), nz + K - s) there with w[s-1].
+// RLX + SIG (stencil_sweepk_signal_relax): the weight is indexed by the stage alone, never by the march, so
+// the up- and the down-marching segment of a chunk apply the same w[s-1] at stage s.
 // SLIVER (sliver_shape() only; fast & kSliver): the last tile column stores at most
 // 16 - 2 XR = 8 columns, so one of its tiles needs 16 lanes of a region row: XR ring lanes, its
 // output columns, the ghost column x = nx, the rest unused.  A SLIVER WORKGROUP runs four such tiles
@@ -352,8 +356,8 @@ __global__ void __launch_bounds__(64 * NW)
     static_assert(!SRC || (!TIER && !UMAX && !HL && !SPLIT && DIAG == 0 && NS == 4 && !TK_SST && !TK_XRING8 &&
                            !TK_PROBE_NOBAR),
                   "SRC: plain or face-signalled launches of the source shapes only");
-    static_assert(!RLX || (SRC && !SIG && !UMAX && !TIER && !HL && !SPLIT && DIAG == 0 && K <= kRelaxWeights),
-                  "RLX: plain launches of the source shapes only");
+    static_assert(!RLX || (SRC && !UMAX && !TIER && !HL && !SPLIT && DIAG == 0 && K <= kRelaxWeights),
+                  "RLX: plain or face-signalled launches of the source shapes only");
     constexpr bool SST = Tl::SSTS && !SIG && !TIER && !HL;
     constexpr int NI = (RY + 1) / 2;  // SST: row pairs per strip
     typedef T V4T __attribute__((ext_vector_type(4)));
@@ -1566,6 +1570,17 @@ int launch_tkstrip_relax(const stencil_layout& l, const void* in, void* out, con
                          int64_t end, int steps, const double* omegas, hipStream_t s) {
     if (!temporal2_supports(l.prob) || (l.prob.flags & (STENCIL_HALO_LO | STENCIL_HALO_HI)))
         return set_error(STENCIL_EUNSUPPORTED, "relaxed sweeps cover the 3D r=1 naive 7-point star without halo flags");
+    return launch_tkstrip_relax_halo(l, in, out, src, begin, end, steps, omegas, s);
+}
+
+// The same shapes on a layout that may carry halo flags (stencil_sweepk_relax_halo): as
+// launch_tkstrip_source_halo is to launch_tkstrip_source.  halo_lo / halo_hi are run-time arguments of the
+// kernel and launch_st's halo rules (halo >= K, the one-round grid of a slab launch, no packed table) apply.
+// A halo side's advanced planes take the source of their own plane and the stage's weight.
+int launch_tkstrip_relax_halo(const stencil_layout& l, const void* in, void* out, const void* src, int64_t begin,
+                              int64_t end, int steps, const double* omegas, hipStream_t s) {
+    if (!temporal2_supports(l.prob))
+        return set_error(STENCIL_EUNSUPPORTED, "relaxed sweeps cover the 3D r=1 naive 7-point star only");
     if (steps < 2 || steps > kRelaxWeights)
         return set_error(STENCIL_EINVAL, "fused relaxed sweeps: steps must be 2..%d (got %d)", kRelaxWeights, steps);
     StripExtras x;
@@ -1582,6 +1597,38 @@ int launch_tkstrip_relax(const stencil_layout& l, const void* in, void* out, con
     default:
         return f32 ? launch_st<RelaxShape<float, 4>>(l, in, out, begin, end, s, x)
                    : launch_st<RelaxShape<double, 4>>(l, in, out, begin, end, s, x);
+    }
+}
+
+// Face-signalled relaxed launches (SRC + SIG + RLX; stencil_sweepk_signal_relax): K = 3 and 4.  Rows per
+// strip by the rule of the source and relax shapes: the largest count, not above the face-signalled source
+// shape's (6 at K = 3, 4 at K = 4), that compiles with no scratch.  Both K keep the signalled source
+// shape's rows in both types (DESIGN.md §5.8 has the table), so the tiles, and with them the adds per face,
+// are the signalled source launch's -- by measurement, not by construction: the table is this launch's own,
+// and so is its geometry query (relax_signal_launch_geometry).  TK_RELAXSIG_ROWS: the compile-time probe of
+// that choice, rows by [fp64][K - 3].  No shape may use scratch.
+#ifndef TK_RELAXSIG_ROWS
+#define TK_RELAXSIG_ROWS {{6, 4}, {6, 4}}
+#endif
+constexpr int kRelaxSignalRows[2][2] = TK_RELAXSIG_ROWS;
+template <typename T, int K>
+using RelaxSignalShape =
+    Shape<T, sizeof(T) == 8 ? 1 : 2, kRelaxSignalRows[sizeof(T) == 8][K - 3], 8, K, kSrc | kSig | kRelax>;
+
+// (x.omega holds the launch's `steps` weights, x.src, x.sig and, gated, x.gate as the signalled source launch's)
+int launch_tkstrip_relax_signal(const stencil_layout& l, const void* in, void* out, int64_t begin, int64_t end,
+                                int steps, const StripExtras& x, hipStream_t s) {
+    if (!temporal2_supports(l.prob))
+        return set_error(STENCIL_EUNSUPPORTED, "face-signalled relaxed sweeps cover the 3D r=1 naive 7-point star only");
+    const bool f32 = l.prob.dtype == STENCIL_F32;
+    switch (steps) {
+    case 3:
+        return f32 ? launch_st<RelaxSignalShape<float, 3>>(l, in, out, begin, end, s, x)
+                   : launch_st<RelaxSignalShape<double, 3>>(l, in, out, begin, end, s, x);
+    case 4:
+        return f32 ? launch_st<RelaxSignalShape<float, 4>>(l, in, out, begin, end, s, x)
+                   : launch_st<RelaxSignalShape<double, 4>>(l, in, out, begin, end, s, x);
+    default: return set_error(STENCIL_EINVAL, "face-signalled relaxed sweeps: steps must be 3 or 4 (got %d)", steps);
     }
 }
 #else

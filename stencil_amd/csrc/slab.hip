@@ -430,6 +430,40 @@ struct HipDev {
         *nsig = n;
         return rc;
     }
+    // ---- relaxed rounds (slab_core.hpp run_relax / run_until_relax) ----
+    static int sweepk_relax(const stencil_layout* l, const void* in, void* out, const void* src, int64_t b, int64_t e,
+                            int k, const double* w, Stream s) {
+        return stencil_sweepk_relax_halo(l, in, out, src, b, e, k, w, s);
+    }
+    // halo_gate's rule on the face-signalled relaxed launch's own tiles
+    static bool relax_halo_gate(const stencil_layout& l, int k, bool confined) {
+        if (confined) return true;
+        int64_t tiles = 0, wg = 0;
+        int slots = 0;
+        if (relax_signal_launch_geometry(l, 0, l.prob.nz, k, &tiles, &wg, &slots) != STENCIL_OK) {
+            clear_error();
+            return false;
+        }
+        return slots > 0 && 2 * tiles <= slots - slots / 32;
+    }
+    static int sweepk_signal_relax(const stencil_layout* l, const void* in, void* out, const void* src, int64_t b,
+                                   int64_t e, int k, const double* w, uint32_t* counters, uint64_t* fsig, int* nsig,
+                                   Stream s) {
+        int32_t n = 0;
+        const int rc = stencil_sweepk_signal_relax(l, in, out, src, b, e, k, w, counters, fsig, &n, s);
+        *nsig = n;
+        return rc;
+    }
+    static int sweepk_signal_relax_gated(const stencil_layout* l, const void* in, void* out, const void* src, int64_t b,
+                                         int64_t e, int k, const double* w, uint32_t* counters, uint64_t* fsig,
+                                         uint32_t need, uint32_t* release, int* nsig, Stream s) {
+        int32_t n = 0;
+        if (knob("STENCIL_SLAB_GATE_SKIP", 0)) need = 0;  // as sweepk_signal_gated
+        const int rc =
+            stencil_sweepk_signal_relax_gated(l, in, out, src, b, e, k, w, counters, fsig, need, release, &n, s);
+        *nsig = n;
+        return rc;
+    }
     // ---- convergence checks (slab_core.hpp run_until) ----
     static int until_fused_steps(const stencil_problem& p, uint32_t block, int32_t norm) {
         return stencil::until_fused_steps(p, block, norm);
@@ -722,6 +756,28 @@ int stencil_slab_source_plan(const stencil_problem* global, uint32_t iterations,
 
 int stencil_slab_source_round_form(const stencil_slab_job* job, int32_t* form) {
     return core::source_round_form<HipDev>(job, form);
+}
+
+int stencil_slab_run_relax(stencil_slab_job* job, uint32_t iterations, const double* omegas, uint32_t period,
+                           uint32_t phase, float* elapsed_ms) {
+    const stencil::SustainedScope sustained(iterations >= stencil::kSustainedSweeps);
+    return core::run_relax<HipDev>(job, iterations, omegas, period, phase, elapsed_ms);
+}
+
+int stencil_slab_run_until_relax(stencil_slab_job* job, uint32_t max_iterations, uint32_t check_every, int32_t norm,
+                                 double tol, const double* omegas, uint32_t period, uint32_t phase,
+                                 uint32_t* iterations_done, double* last_norm, int* converged, float* elapsed_ms) {
+    const stencil::SustainedScope sustained(max_iterations >= stencil::kSustainedSweeps);
+    return core::run_until_relax<HipDev>(job, max_iterations, check_every, norm, tol, omegas, period, phase,
+                                         iterations_done, last_norm, converged, elapsed_ms);
+}
+
+int stencil_slab_relax_plan(const stencil_problem* global, uint32_t iterations, int64_t* rounds, int32_t* steps) {
+    return core::source_plan<HipDev>(global, iterations, rounds, steps);
+}
+
+int stencil_slab_relax_round_form(const stencil_slab_job* job, int32_t* form) {
+    return core::relax_round_form<HipDev>(job, form);
 }
 
 int stencil_slab_download(stencil_slab_job* job, void* host, int64_t host_row, int64_t host_rows) {

@@ -37,7 +37,8 @@
 // fake device (tests/cpu_slab/: synchronous plane copies and the oracle's
 // sweep, an in-process mailbox for send/recv), which runs this same round
 // logic at world 2/3 under `pytest -m "not gpu"` (tests/cpu_slab_source/: the
-// same fake device with a source sweep, for the source rounds).
+// same fake device with a source sweep, for the source rounds;
+// tests/cpu_slab_relax/: with a relaxed sweep too, for the relaxed rounds).
 #pragma once
 
 #include <algorithm>
@@ -179,6 +180,9 @@ struct Job {
     // face-signalled source rounds of a gated job: 1 = their launches are gated too, 0 = they wait for the
     // exchange's event (the source launch's own tiles do not meet the gate's rule), -1 = not decided yet
     int source_gate = -1;
+    // the same decision for the face-signalled relaxed rounds, on the relaxed launch's own tiles (its rows per
+    // strip come from a table of its own, so the answer is kept apart from source_gate)
+    int relax_gate = -1;
 };
 
 constexpr int kInflight = 8;  // rounds queued ahead of the last completed exchange
@@ -1847,6 +1851,157 @@ int source_plan(const stencil_problem* global, uint32_t iterations, int64_t* rou
 
 template <class Dev, class JobT>
 int source_round_form(const JobT* job, int32_t* form) {
+    if (!job || !form) return set_error(STENCIL_EINVAL, "null argument");
+    SLAB_TRY(check_source_job(*job, false));
+    *form = source_round_form_of(*job);
+    return STENCIL_OK;
+}
+
+// ---- relaxed rounds (stencil_slab_run_relax / run_until_relax) ----------------
+// u' = u + w (S(u) + g - u) across the slabs with a weight per sweep: the source rounds
+// with launches that also relax.  g is set_source's grid; rounds take Ks = min(K, STENCIL_SOURCE_MAX_STEPS)
+// sweeps and the halo depth stays K, as the source rounds'.  Sweep i of a call takes
+// omegas[(phase + i) % period]; every slab of a round takes the same weights, so a halo side's advanced planes
+// are relaxed with the weights their owner applies.  The weights are arguments of the launches: nothing is
+// uploaded per round.
+// Everything below uses Dev members neither the plain nor the source rounds do (sweepk_relax, ...): it is
+// instantiated by slab.hip and by the CPU test build of tests/cpu_slab_relax/, never by tests/cpu_slab/ or
+// tests/cpu_slab_source/.
+struct RoundWeights {
+    double w[STENCIL_SOURCE_MAX_STEPS] = {};  // sweep i of the round takes w[i]
+};
+template <class Dev>
+struct RelaxSweep {
+    RoundWeights rw;
+    int begin(Slab<Dev>&) const { return STENCIL_OK; }
+    int operator()(Slab<Dev>& s, const void* src, void* dst, int64_t b, int64_t e, int k,
+                   typename Dev::Stream st) const {
+        return Dev::sweepk_relax(&s.l, src, dst, s.src, b, e, k, rw.w, st);
+    }
+};
+template <class Dev>
+struct RelaxSignal {
+    RoundWeights rw;
+    int begin(Slab<Dev>&) const { return STENCIL_OK; }
+    int operator()(const Job<Dev>& j, Slab<Dev>& s, const void* src, void* dst, int k, int* nsig) const {
+        if (j.gate)
+            return Dev::sweepk_signal_relax_gated(&s.l, src, dst, s.src, 0, s.n, k, rw.w, s.counters, s.fsig, s.xseq,
+                                                  s.tflag, nsig, s.sb);
+        return Dev::sweepk_signal_relax(&s.l, src, dst, s.src, 0, s.n, k, rw.w, s.counters, s.fsig, nsig, s.sb);
+    }
+};
+
+// A schedule: `period` finite weights
+inline int check_weights(const double* omegas, uint32_t period) {
+    if (!omegas) return set_error(STENCIL_EINVAL, "null weights (omegas)");
+    if (period == 0) return set_error(STENCIL_EINVAL, "the schedule's period must be at least 1");
+    for (uint32_t i = 0; i < period; ++i)
+        if (!std::isfinite(omegas[i]))
+            return set_error(STENCIL_EINVAL, "weight %u of the schedule is not a finite number", i);
+    return STENCIL_OK;
+}
+struct Schedule {
+    const double* omegas = nullptr;
+    uint32_t period = 1;
+    // the weights of `k` sweeps from schedule index `at`
+    RoundWeights take(uint64_t at, int k) const {
+        RoundWeights r;
+        for (int i = 0; i < k && i < STENCIL_SOURCE_MAX_STEPS; ++i) r.w[i] = omegas[(at + uint64_t(i)) % period];
+        return r;
+    }
+};
+
+// One relaxed round of `k` sweeps with the weights rw.  Its form is the source round's (source_round_form_of:
+// the one knob STENCIL_SLAB_SOURCE_SIGNAL governs both), and so is the handling of the gate and of gate_chain;
+// whether a gated job gates the relaxed launches is decided once per job on the relaxed launch's own tiles
+// (Dev::relax_halo_gate; Job::relax_gate).
+template <class Dev>
+int one_relax_round(Job<Dev>& j, int k, bool full, const RoundWeights& rw) {
+    SLAB_TRY(throttle(j));
+    if (full && source_round_form_of(j) == STENCIL_SLAB_FORM_SIGNALLED) {
+        if (j.gate && j.relax_gate < 0) {
+            bool fits = true;
+            for (Slab<Dev>& s : j.s) {
+                SLAB_FAIL(j, Dev::set_device(s.device));
+                fits = fits && Dev::relax_halo_gate(s.l, k, j.confine);
+            }
+            j.relax_gate = fits ? 1 : 0;
+        }
+        const bool job_gate = j.gate;
+        j.gate = job_gate && j.relax_gate == 1;
+        if (!j.gate) j.gate_chain = false;
+        const int rc = slab_round_signal(j, k, RelaxSignal<Dev>{rw});  // (sets gate_chain from this round's gate)
+        j.gate = job_gate;
+        SLAB_FAIL(j, rc);
+    } else {
+        j.gate_chain = false;  // only a gated launch may follow a gated launch unsynchronised
+        SLAB_FAIL(j, slab_round(j, k, RelaxSweep<Dev>{rw}));
+    }
+    SLAB_FAIL(j, mark_round(j));
+    return STENCIL_OK;
+}
+
+// `sweeps` relaxed sweeps from schedule index `at`: full rounds of Ks, then one shorter round.
+template <class Dev>
+int relax_rounds(Job<Dev>& j, uint32_t sweeps, const Schedule& sch, uint64_t at) {
+    uint32_t done = 0;
+    const uint32_t k = uint32_t(source_steps(j));
+    for (; done + k <= sweeps; done += k) SLAB_TRY(one_relax_round(j, int(k), true, sch.take(at + done, int(k))));
+    if (done < sweeps) SLAB_TRY(one_relax_round(j, int(sweeps - done), false, sch.take(at + done, int(sweeps - done))));
+    return STENCIL_OK;
+}
+// run_until's rounds policy: the schedule index runs on across the blocks, and the checking sweep takes its
+// own weight
+template <class Dev>
+struct RelaxRounds {
+    Schedule sch;
+    mutable uint64_t at = 0;  // schedule index of the next sweep
+    int fused(const Job<Dev>&, uint32_t, int32_t) const { return 0; }  // the check is always the un-fused one
+    int rounds(Job<Dev>& j, uint32_t sweeps) const {
+        SLAB_TRY(relax_rounds(j, sweeps, sch, at));
+        at += sweeps;
+        return STENCIL_OK;
+    }
+    int single(Job<Dev>& j) const {
+        SLAB_TRY(one_relax_round(j, 1, false, sch.take(at, 1)));
+        at += 1;
+        return STENCIL_OK;
+    }
+};
+
+template <class Dev, class JobT>
+int run_relax(JobT* job, uint32_t iterations, const double* omegas, uint32_t period, uint32_t phase, float* elapsed_ms) {
+    if (!job) return set_error(STENCIL_EINVAL, "null job");
+    SLAB_TRY(check_source_job(*job, true));
+    SLAB_TRY(check_weights(omegas, period));
+    SLAB_TRY(sync_bounded(*job));
+    const auto t0 = std::chrono::steady_clock::now();
+    SLAB_TRY(relax_rounds(*job, iterations, Schedule{omegas, period}, phase));
+    SLAB_TRY(sync_bounded(*job));
+    if (job->signal) SLAB_FAIL(*job, check_signal_timeouts(*job));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (elapsed_ms) *elapsed_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    clear_error();
+    return STENCIL_OK;
+}
+
+template <class Dev, class JobT>
+int run_until_relax(JobT* job, uint32_t max_iterations, uint32_t check_every, int32_t norm, double tol,
+                    const double* omegas, uint32_t period, uint32_t phase, uint32_t* iterations_done, double* last_norm,
+                    int* converged, float* elapsed_ms) {
+    if (!job) return set_error(STENCIL_EINVAL, "null job");
+    SLAB_TRY(check_source_job(*job, true));
+    SLAB_TRY(check_weights(omegas, period));
+    RelaxRounds<Dev> sweeps;
+    sweeps.sch = Schedule{omegas, period};
+    sweeps.at = phase;
+    return run_until<Dev, JobT, RelaxRounds<Dev>>(job, max_iterations, check_every, norm, tol, iterations_done, last_norm,
+                                                  converged, elapsed_ms, sweeps);
+}
+
+// a full relaxed round's form: the source round's rule (source_round_form_of)
+template <class Dev, class JobT>
+int relax_round_form(const JobT* job, int32_t* form) {
     if (!job || !form) return set_error(STENCIL_EINVAL, "null argument");
     SLAB_TRY(check_source_job(*job, false));
     *form = source_round_form_of(*job);

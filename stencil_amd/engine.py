@@ -506,6 +506,37 @@ class JacobiEngine:
                                                  w if n else None, _stream_handle(stream)),
                    "stencil_sweepk_relax", lib=self.lib)
 
+    def sweepk_relax_halo(self, src_grid: torch.Tensor, dst_grid: torch.Tensor, begin: int, end: int, omegas,
+                          stream=None) -> None:
+        """sweepk_relax on a layout that may carry halo flags
+        (stencil_sweepk_relax_halo): a halo side's planes are advanced on chip,
+        each with the source grid's halo plane and the stage's weight."""
+        w, n = self._weights(omegas)
+        _lib.check(self.lib.stencil_sweepk_relax_halo(ctypes.byref(self.layout), ctypes.c_void_p(src_grid.data_ptr()),
+                                                      ctypes.c_void_p(dst_grid.data_ptr()), self._source_ptr(), begin,
+                                                      end, n, w if n else None, _stream_handle(stream)),
+                   "stencil_sweepk_relax_halo", lib=self.lib)
+
+    def sweepk_signal_relax(self, src_grid: torch.Tensor, dst_grid: torch.Tensor, begin: int, end: int, omegas,
+                            counters: torch.Tensor, stream=None, face_signal: "FaceSignal | None" = None,
+                            gated: bool = False, gate_need: int = 0) -> int:
+        """sweepk_signal_source with weights (stencil_sweepk_signal_relax; 3
+        or 4 of them): `dst` as sweepk_relax_halo's, counters, face signal and
+        gate as sweepk_signal_source's; returns adds per face."""
+        w, nw = self._weights(omegas)
+        n = ctypes.c_int32(0)
+        args = (ctypes.byref(self.layout), ctypes.c_void_p(src_grid.data_ptr()), ctypes.c_void_p(dst_grid.data_ptr()),
+                self._source_ptr(), begin, end, nw, w if nw else None, ctypes.c_void_p(counters.data_ptr()),
+                face_signal.ptr if face_signal is not None else None)
+        if gated:
+            _lib.check(self.lib.stencil_sweepk_signal_relax_gated(*args, gate_need, None, ctypes.byref(n),
+                                                                  _stream_handle(stream)),
+                       "stencil_sweepk_signal_relax_gated", lib=self.lib)
+        else:
+            _lib.check(self.lib.stencil_sweepk_signal_relax(*args, ctypes.byref(n), _stream_handle(stream)),
+                       "stencil_sweepk_signal_relax", lib=self.lib)
+        return int(n.value)
+
     def iterate_relax(self, iterations: int, omegas, phase: int = 0, stream=None, timed: bool = False):
         """iterate_source() with sweep i relaxed by omegas[(phase + i) %
         len(omegas)] (stencil_iterate_relax; one number: a constant weight);
@@ -841,6 +872,47 @@ class SlabJob:
         1 face-signalled, 3 serial (stencil_slab_source_round_form)."""
         f = ctypes.c_int32(-1)
         _lib.check(self.lib.stencil_slab_source_round_form(self.job, ctypes.byref(f)), "stencil_slab_source_round_form",
+                   lib=self.lib)
+        return int(f.value)
+
+    # u' = u + w (S(u) + g - u) across the slabs (stencil_slab_*_relax), g being set_source()'s grid
+    def run_relax(self, iterations: int, omegas, phase: int = 0) -> float:
+        """`iterations` relaxed sweeps, sweep i with omegas[(phase + i) %
+        len(omegas)] (stencil_slab_run_relax; one number: a constant weight);
+        returns the host wall time of the rounds (ms)."""
+        w, n = JacobiEngine._weights(omegas)
+        ms = ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_slab_run_relax(self.job, iterations, w if n else None, n, phase, ctypes.byref(ms)),
+                   "stencil_slab_run_relax", lib=self.lib)
+        return float(ms.value)
+
+    def run_until_relax(self, tol: float, max_iterations: int, omegas, check_every: int = 100, norm: str = "max",
+                        phase: int = 0) -> "UntilResult":
+        """run_until_source() on relaxed sweeps (stencil_slab_run_until_relax);
+        make check_every a multiple of len(omegas)."""
+        w, n = JacobiEngine._weights(omegas)
+        done, conv = ctypes.c_uint32(0), ctypes.c_int(0)
+        last, ms = ctypes.c_double(0.0), ctypes.c_float(0.0)
+        _lib.check(self.lib.stencil_slab_run_until_relax(self.job, max_iterations, check_every, _lib.NORM_NAMES[norm],
+                                                         tol, w if n else None, n, phase, ctypes.byref(done),
+                                                         ctypes.byref(last), ctypes.byref(conv), ctypes.byref(ms)),
+                   "stencil_slab_run_until_relax", lib=self.lib)
+        return UntilResult(None, int(done.value), bool(conv.value), float(last.value), float(ms.value))
+
+    def relax_plan(self, iterations: int) -> dict:
+        """run_relax(iterations) as rounds, and the sweeps of a full round
+        (stencil_slab_relax_plan, host only; equals source_plan)."""
+        prob = self.spec.problem(*self.shape)
+        rounds, steps = ctypes.c_int64(0), ctypes.c_int32(0)
+        _lib.check(self.lib.stencil_slab_relax_plan(ctypes.byref(prob), iterations, ctypes.byref(rounds),
+                                                    ctypes.byref(steps)), "stencil_slab_relax_plan", lib=self.lib)
+        return {"rounds": int(rounds.value), "steps": int(steps.value)}
+
+    def relax_round_form(self) -> int:
+        """The form of a full relaxed round: 0 boundary + interior launches,
+        1 face-signalled, 3 serial (stencil_slab_relax_round_form)."""
+        f = ctypes.c_int32(-1)
+        _lib.check(self.lib.stencil_slab_relax_round_form(self.job, ctypes.byref(f)), "stencil_slab_relax_round_form",
                    lib=self.lib)
         return int(f.value)
 
