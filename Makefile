@@ -26,6 +26,8 @@ CXXFLAGS ?= -O2 -std=c++17 -Wall -Wextra -ffp-contract=off -Iinclude
 LIB := stencil_amd/libstencil_hip.so
 LIB_DBG := stencil_amd/libstencil_hip_debug.so
 CLI := build/bin/stencil_main
+# every .hip of csrc: api.hip, slab.hip and the kernels_*.hip families (kernels_mg.hip: the multigrid transfer
+# kernels and the stencil_mg_* driver, default flags)
 SRCS := $(wildcard stencil_amd/csrc/*.hip)
 OBJ ?= build/obj
 # kernels_boxk_probe.hip (a code-generation probe) is built twice, with and without SLP

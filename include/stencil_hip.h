@@ -649,6 +649,122 @@ int stencil_sweepk_signal_relax_gated(const stencil_layout* l, const void* in, v
                                       uint32_t* counters, uint64_t* face_signal, uint32_t gate_need,
                                       uint32_t* release_flag, int32_t* signals_per_face, void* stream);
 
+/* Geometric multigrid for the 7-point Poisson solve on one GPU (DESIGN.md
+ * §5.9; kernels_mg.hip): the relaxed sweeps above are the smoother, the calls
+ * below compute residuals, move them between a fine grid and its coarsening,
+ * and run V-cycles.  Scope everywhere: stencil_sweepk_source's (3D 7-point
+ * star, r = 1, naive order, fp32 / fp64, flags == 0, kernel AUTO or TEMPORALK).
+ * Every formula is a sequence of separately rounded IEEE operations in the
+ * grid's type T, never an fma: results are bit for bit defined by the data.
+ *
+ * Coarsening is vertex-centred: a fine problem with odd interior extents
+ * nx, ny, nz >= 3 has the coarse problem ((nx-1)/2, (ny-1)/2, (nz-1)/2), and
+ * coarse interior cell (X, Y, Z) sits on fine interior cell (2X+1, 2Y+1, 2Z+1).
+ * The coarse grid has its own stencil_layout (stencil_layout_init of the coarse
+ * problem; its pitch and origin are unrelated to the fine grid's).
+ *
+ * Residual, in the library's scaling r = (h^2 / 6) (f + Laplace_h u): at every
+ * interior cell c
+ *   r(c) = fl( J(c) - u(c) ),  J(c) = fl( fl( sum6(u, c) * avg ) + g(c) )
+ * -- exactly the `d` of the relaxed sweep.  It reads u's ghost ring and g's
+ * interior; no residual of a ghost cell exists.
+ *
+ * Restricted residual (the coarse problem's source): the coarse error equation
+ * is e = S(e) + g_c with g_c = 4 R(r), R the 27-point full weighting, taken
+ * separably.  The 1-D operator along an axis is
+ *   A(X) = fl( fl( v(i-1) + v(i+1) ) + fl( v(i) + v(i) ) ),  i = 2X + 1,
+ * applied along x to r, then along y to that, then along z; then
+ * g_c = fl( 0.0625 * that ).  Every fine index touched (2X .. 2X+2) is interior.
+ *
+ * Prolongation and correction: trilinear and separable, x, then y, then z.
+ * Along an axis fine index i odd takes coarse cell (i-1)/2 EXACTLY (a copy, not
+ * 0.5 (e + e), which differs for huge values); i even takes
+ * fl( 0.5 * fl( e(i/2 - 1) + e(i/2) ) ), coarse indices -1 and m being e's ghost
+ * cells (the ghost ring's edges and corners included).  Then
+ * u(c) = fl( u(c) + p(c) ), in place, at interior cells only.
+ *
+ * stencil_coarsen_problem (host only): *coarse = the coarsening of *fine.
+ * STENCIL_EINVAL: an even extent or an extent < 3, NULL arguments;
+ * STENCIL_EUNSUPPORTED outside the scope (the message names the restriction).
+ *
+ * stencil_residual_norms: stencil_diff_norms' outputs, argument rules,
+ * determinism and NaN rule for d = double(r(c)), per plane of [begin, end):
+ * max_abs[z - begin] = max |d|, sum_sq[z - begin] = sum d*d over the plane's
+ * interior cells.  r is not stored.  This is the stopping criterion of a
+ * multigrid solve (the update norm of the *_until calls means nothing across
+ * cycles).
+ *
+ * stencil_restrict_residual: reads u and src (= g) on the fine layout lf,
+ * stores g_c at the interior cells of coarse planes [cbegin, cend) of
+ * coarse_src (layout lc) and nothing else; the residual never reaches memory.
+ * stencil_prolong_add: u += P(e) at the interior cells of fine planes
+ * [begin, end), in place; never stores to a ghost cell, to padding or to e.
+ * STENCIL_EINVAL for both: lc is not the coarsening of lf (or either is not
+ * stencil_layout_init's layout of its problem), a dtype mismatch, NULL grids,
+ * aliased grids, a bad range.
+ *
+ * The hierarchy, stencil_mg: levels 0 (fine) .. L-1, each with two field grids
+ * (the relaxed jobs ping-pong) and a source grid, allocated zeroed on the
+ * current device.  stencil_mg_create: levels = 0 coarsens while every extent is
+ * odd and >= 3; a count above that is STENCIL_EINVAL; a level whose shape the
+ * relaxed job cannot run refuses the count with STENCIL_EUNSUPPORTED and a
+ * message (nothing is ever launched on such a shape).  stencil_mg_level: the
+ * level's layout, the grid that CURRENTLY holds its field, its source grid
+ * (each output optional).  stencil_mg_upload / stencil_mg_download move the
+ * fine field and / or the fine source (either may be NULL, not both) as dense
+ * ghost-padded host arrays, as stencil_upload does; the field's ghost cells are
+ * the Dirichlet data.
+ *
+ * stencil_mg_vcycle: one V-cycle.  The coarsest level runs coarse_sweeps
+ * relaxed sweeps.  Every other level l: `pre` relaxed sweeps; the restricted
+ * residual into level l+1's source; level l+1's field set to zero, ghost cells
+ * included; the cycle on level l+1; prolong-add into level l; `post` relaxed
+ * sweeps.  Every smoothing run is stencil_iterate_relax's job on that level's
+ * layout with omegas[i % period] for its sweep i (phase 0 in every run).  A
+ * fixed sequence of bitwise-defined operations: the result is bitwise defined.
+ * stencil_mg_solve: cycles in blocks of min(check_every, max_cycles - done),
+ * each followed by the scalar norm (stencil_diff_norms' rule: STENCIL_NORM_MAX
+ * or STENCIL_NORM_L2) of the fine stencil_residual_norms; stopping rule and edge
+ * cases are stencil_iterate_until's (*converged = 1 when norm <= tol; 0 when
+ * the norm is NaN or max_cycles are done; max_cycles = 0: *cycles_done = 0,
+ * *converged = 0, *last_norm = +inf; not converging is STENCIL_OK).
+ * STENCIL_EINVAL: NULL hierarchy or params, NULL omegas, period = 0, a weight
+ * that is NaN or infinite, check_every = 0, tol < 0 or NaN, an unknown norm.
+ * stencil_mg_plan (host only, no device): the kernel launches of one cycle --
+ * stencil_relax_plan of every smoothing run plus one restriction and one
+ * prolongation launch per level but the coarsest (the zero fill is a memset) --
+ * and the level count `levels` resolves to.
+ * All argument errors fire before a device is touched. */
+typedef struct stencil_mg stencil_mg;
+typedef struct stencil_mg_params {
+    uint32_t pre;            /* relaxed sweeps before the coarse-grid correction */
+    uint32_t post;           /* ... and after it */
+    uint32_t coarse_sweeps;  /* relaxed sweeps on the coarsest level */
+    uint32_t period;         /* weights in `omegas` */
+    const double* omegas;    /* host array; sweep i of every smoothing run takes omegas[i % period] */
+} stencil_mg_params;
+int stencil_coarsen_problem(const stencil_problem* fine, stencil_problem* coarse);
+int stencil_residual_norms(const stencil_layout* l, const void* u, const void* src, int64_t begin, int64_t end,
+                           double* max_abs, double* sum_sq, void* stream);
+int stencil_restrict_residual(const stencil_layout* lf, const void* u, const void* src, const stencil_layout* lc,
+                              void* coarse_src, int64_t cbegin, int64_t cend, void* stream);
+int stencil_prolong_add(const stencil_layout* lc, const void* e, const stencil_layout* lf, void* u, int64_t begin,
+                        int64_t end, void* stream);
+int stencil_mg_create(const stencil_problem* fine, int32_t levels, stencil_mg** mg);
+int stencil_mg_destroy(stencil_mg* mg);
+int stencil_mg_levels(const stencil_mg* mg, int32_t* levels);
+int stencil_mg_level(const stencil_mg* mg, int32_t level, stencil_layout* out, void** field, void** source);
+int stencil_mg_upload(stencil_mg* mg, const void* field, const void* source, int64_t host_row, int64_t host_rows,
+                      void* stream);
+int stencil_mg_download(const stencil_mg* mg, void* field, void* source, int64_t host_row, int64_t host_rows,
+                        void* stream);
+int stencil_mg_vcycle(stencil_mg* mg, const stencil_mg_params* params, void* stream);
+int stencil_mg_solve(stencil_mg* mg, const stencil_mg_params* params, uint32_t max_cycles, uint32_t check_every,
+                     int32_t norm, double tol, void* stream, uint32_t* cycles_done, double* last_norm, int* converged,
+                     float* elapsed_ms);
+int stencil_mg_plan(const stencil_problem* fine, int32_t levels, const stencil_mg_params* params, int64_t* launches,
+                    int32_t* levels_out);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,

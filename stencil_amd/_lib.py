@@ -73,6 +73,9 @@ EXPORTED_SYMBOLS = (
     "stencil_sweepk_relax_halo", "stencil_sweepk_signal_relax", "stencil_sweepk_signal_relax_gated",
     "stencil_slab_run_relax", "stencil_slab_run_until_relax", "stencil_slab_relax_plan",
     "stencil_slab_relax_round_form",
+    "stencil_coarsen_problem", "stencil_residual_norms", "stencil_restrict_residual", "stencil_prolong_add",
+    "stencil_mg_create", "stencil_mg_destroy", "stencil_mg_levels", "stencil_mg_level", "stencil_mg_upload",
+    "stencil_mg_download", "stencil_mg_vcycle", "stencil_mg_solve", "stencil_mg_plan",
 )
 
 
@@ -86,6 +89,12 @@ class Layout(Structure):
     _fields_ = [("prob", Problem), ("row", c_int64), ("plane", c_int64), ("planes", c_int64),
                 ("zghost", c_int64), ("rows", c_int64), ("origin", c_int64), ("elems", c_int64),
                 ("bytes", c_int64)]
+
+
+class MgParams(Structure):
+    """stencil_mg_params: the V-cycle's sweep counts and its weight schedule."""
+    _fields_ = [("pre", c_uint32), ("post", c_uint32), ("coarse_sweeps", c_uint32), ("period", c_uint32),
+                ("omegas", POINTER(c_double))]
 
 
 class MatrixView(Structure):
@@ -129,7 +138,7 @@ def load(debug: bool | None = None) -> ctypes.CDLL:
             "(run `make` or `python -c 'import __graft_entry__ as g; g.build()'`)")
     lib = ctypes.CDLL(path)
     for name, (res, args) in {**signatures(), **slab_until_signatures(), **slab_source_signatures(),
-                              **slab_relax_signatures()}.items():
+                              **slab_relax_signatures(), **mg_signatures()}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -303,6 +312,28 @@ def slab_relax_signatures() -> dict:
                                                  POINTER(c_int), POINTER(c_float)]),
         "stencil_slab_relax_plan": (c_int, [POINTER(Problem), c_uint32, POINTER(c_int64), POINTER(c_int32)]),
         "stencil_slab_relax_round_form": (c_int, [c_void_p, POINTER(c_int32)]),
+    }
+
+
+def mg_signatures() -> dict:
+    """The multigrid entry points (stencil_amd/multigrid.py)."""
+    P, L, M = POINTER(Problem), POINTER(Layout), POINTER(MgParams)
+    return {
+        "stencil_coarsen_problem": (c_int, [P, P]),
+        "stencil_residual_norms": (c_int, [L, c_void_p, c_void_p, c_int64, c_int64, POINTER(c_double), POINTER(c_double),
+                                           c_void_p]),
+        "stencil_restrict_residual": (c_int, [L, c_void_p, c_void_p, L, c_void_p, c_int64, c_int64, c_void_p]),
+        "stencil_prolong_add": (c_int, [L, c_void_p, L, c_void_p, c_int64, c_int64, c_void_p]),
+        "stencil_mg_create": (c_int, [P, c_int32, POINTER(c_void_p)]),
+        "stencil_mg_destroy": (c_int, [c_void_p]),
+        "stencil_mg_levels": (c_int, [c_void_p, POINTER(c_int32)]),
+        "stencil_mg_level": (c_int, [c_void_p, c_int32, L, POINTER(c_void_p), POINTER(c_void_p)]),
+        "stencil_mg_upload": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+        "stencil_mg_download": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+        "stencil_mg_vcycle": (c_int, [c_void_p, M, c_void_p]),
+        "stencil_mg_solve": (c_int, [c_void_p, M, c_uint32, c_uint32, c_int32, c_double, c_void_p, POINTER(c_uint32),
+                                     POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
+        "stencil_mg_plan": (c_int, [P, c_int32, M, POINTER(c_int64), POINTER(c_int32)]),
     }
 
 
