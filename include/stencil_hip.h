@@ -765,6 +765,82 @@ int stencil_mg_solve(stencil_mg* mg, const stencil_mg_params* params, uint32_t m
 int stencil_mg_plan(const stencil_problem* fine, int32_t levels, const stencil_mg_params* params, int64_t* launches,
                     int32_t* levels_out);
 
+/* Full multigrid (FMG) start-up of the same solve: the
+ * problem is solved on the coarsest level, the solution interpolated one level
+ * up as the starting guess, a few V-cycles run there, and so on up to the fine
+ * level -- the solution down to discretization accuracy in one pass, whatever
+ * the fine field held.  Scope, indices and rounding rules are those above: every
+ * operation is rounded separately in T and is never an fma.  A fine extent
+ * n = 2m + 1 has the coarse extent m; ghost cells are index -1 and n on the
+ * fine grid, -1 and m on the coarse grid; coarse cell X sits on fine 2X + 1, so
+ * coarse ghost -1 sits on fine ghost -1 and coarse ghost m on fine ghost n.
+ *
+ * Coarse source: g_c = fl( 0.0625 * A_z(A_y(A_x(g))) ), the 1-D operator A
+ * above applied to g's interior directly (= 4 R(g): g = h^2 f / 6 and the
+ * coarse h is 2h).  Interior cells only.
+ *
+ * Coarse Dirichlet data: every cell (X, Y, Z) of the coarse ghost shell -- the
+ * padded (mz+2)(my+2)(mx+2) box minus its interior, edges and corners included
+ * -- is an exact copy of the fine ghost-shell cell (2X+1, 2Y+1, 2Z+1).
+ *
+ * Cubic prolongation (a set, not an add): separable, x, then y, then z; the x
+ * pass runs over every coarse row, ghost rows and planes included.  Along an
+ * axis with the coarse line c(-1 .. m), fine index i odd takes c((i-1)/2)
+ * exactly.  Fine index i even, k = i/2:
+ *   m = 1:   fl( 0.5 * fl( c(k-1) + c(k) ) );
+ *   m >= 2:  four consecutive nodes p0..p3 with exact integer weights w0..w3,
+ *            k = 0:      c(-1 .. 2),     ( 5, 15, -5,  1)
+ *            k = m:      c(m-3 .. m),    ( 1, -5, 15,  5)
+ *            otherwise:  c(k-2 .. k+1),  (-1,  9,  9, -1)
+ *            value = fl( 0.0625 * fl( fl( fl(w0 p0) + fl(w1 p1) )
+ *                                   + fl( fl(w2 p2) + fl(w3 p3) ) ) ).
+ * It READS THE EDGES AND CORNERS of the coarse ghost ring (fine cell (0, 0, z)
+ * uses coarse (-1, -1, .)), cells no sweep ever reads: a caller of
+ * stencil_mg_fmg must supply them in the fine field's ghost shell -- they are
+ * the boundary data on the domain's edges.
+ *
+ * stencil_restrict_source: g_c of src (layout lf) into the interior cells of
+ * coarse planes [cbegin, cend) of coarse_src (layout lc), nothing else.
+ * stencil_inject_ghosts: the coarse Dirichlet data of u (lf) into the shell
+ * cells of uc (lc), nothing else: no interior cell, no row padding.
+ * stencil_prolong_cubic: the cubic prolongation of e (lc) stored at the interior
+ * cells of fine planes [begin, end) of u (lf), nothing else; u is not read.
+ * Argument rules of all three: stencil_restrict_residual's / stencil_prolong_add's
+ * (STENCIL_EINVAL: lc is not the coarsening of lf, a layout that is not
+ * stencil_layout_init's, a dtype mismatch, NULL grids, aliased grids, a bad
+ * range).  No atomics; results do not depend on tiling or timing.
+ *
+ * stencil_mg_fmg: the pass on a hierarchy of L levels.
+ *   1. For l = 0 .. L-2: level l+1's source = the coarse source of level l's
+ *      source; both field grids of level l+1 zeroed; level l's field ghost
+ *      shell injected into both field grids of level l+1.  Level 0's ghost
+ *      shell is the caller's; level 0's interior is ignored and overwritten.
+ *   2. Level L-1: coarse_sweeps relaxed sweeps from its zero interior (L = 1:
+ *      the whole pass, on level 0 with its interior zeroed first).
+ *   3. For l = L-2 .. 0: level l's interior = the cubic prolongation of level
+ *      l+1's field; both field grids of level l+1 zeroed entirely (so that later
+ *      V-cycles find the zero ghost cells they rely on); `cycles` V-cycles
+ *      started at level l (stencil_mg_vcycle's recursion from that level; it
+ *      overwrites only sources of levels > l, which are consumed).  cycles = 0
+ *      is allowed.
+ * After the pass the field and the source of every level are bitwise defined,
+ * and every level >= 1 has zero ghost cells in both grids, as after creation.
+ * STENCIL_EINVAL as stencil_mg_vcycle.
+ * stencil_mg_fmg_plan (host only): the kernel launches of the pass -- per level
+ * but the coarsest one source restriction, one injection and one cubic
+ * prolongation, stencil_relax_plan of the coarsest run, and `cycles` times the
+ * launches of a V-cycle started at each level l < L-1 (stencil_mg_plan's count
+ * from that level down); memsets are not counted -- and the level count.
+ * All argument errors fire before a device is touched. */
+int stencil_restrict_source(const stencil_layout* lf, const void* src, const stencil_layout* lc, void* coarse_src,
+                            int64_t cbegin, int64_t cend, void* stream);
+int stencil_inject_ghosts(const stencil_layout* lf, const void* u, const stencil_layout* lc, void* uc, void* stream);
+int stencil_prolong_cubic(const stencil_layout* lc, const void* e, const stencil_layout* lf, void* u, int64_t begin,
+                          int64_t end, void* stream);
+int stencil_mg_fmg(stencil_mg* mg, const stencil_mg_params* params, uint32_t cycles, void* stream);
+int stencil_mg_fmg_plan(const stencil_problem* fine, int32_t levels, const stencil_mg_params* params, uint32_t cycles,
+                        int64_t* launches, int32_t* levels_out);
+
 /* A plain device copy kernel (read n bytes, write n bytes) used by bench.py to
  * calibrate attainable HBM bandwidth on the box. */
 int stencil_copy_bandwidth(void* dst, const void* src, int64_t bytes, int reps, void* stream,

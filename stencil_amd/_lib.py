@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "stencil_coarsen_problem", "stencil_residual_norms", "stencil_restrict_residual", "stencil_prolong_add",
     "stencil_mg_create", "stencil_mg_destroy", "stencil_mg_levels", "stencil_mg_level", "stencil_mg_upload",
     "stencil_mg_download", "stencil_mg_vcycle", "stencil_mg_solve", "stencil_mg_plan",
+    "stencil_restrict_source", "stencil_inject_ghosts", "stencil_prolong_cubic", "stencil_mg_fmg", "stencil_mg_fmg_plan",
 )
 
 
@@ -334,6 +335,11 @@ def mg_signatures() -> dict:
         "stencil_mg_solve": (c_int, [c_void_p, M, c_uint32, c_uint32, c_int32, c_double, c_void_p, POINTER(c_uint32),
                                      POINTER(c_double), POINTER(c_int), POINTER(c_float)]),
         "stencil_mg_plan": (c_int, [P, c_int32, M, POINTER(c_int64), POINTER(c_int32)]),
+        "stencil_restrict_source": (c_int, [L, c_void_p, L, c_void_p, c_int64, c_int64, c_void_p]),
+        "stencil_inject_ghosts": (c_int, [L, c_void_p, L, c_void_p, c_void_p]),
+        "stencil_prolong_cubic": (c_int, [L, c_void_p, L, c_void_p, c_int64, c_int64, c_void_p]),
+        "stencil_mg_fmg": (c_int, [c_void_p, M, c_uint32, c_void_p]),
+        "stencil_mg_fmg_plan": (c_int, [P, c_int32, M, c_uint32, POINTER(c_int64), POINTER(c_int32)]),
     }
 
 

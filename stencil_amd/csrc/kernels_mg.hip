@@ -224,6 +224,200 @@ __global__ void __launch_bounds__(kPX * kPY)
     }
 }
 
+// ---- full multigrid: the coarse problems and the cubic prolongation ----
+
+constexpr int kSrcCells = (kMgRW * kMgRH + kMgThreads - 1) / kMgThreads;  // cells of g per lane and fine plane
+
+// g_c = fl(0.0625 * A_z(A_y(A_x(g)))): restrict_residual_kernel's march with g in the residual's place.  The
+// fine tile has no ring (the weighting of interior coarse cells touches interior fine cells only); plane z + 1
+// is fetched into registers while plane z is weighed, and the two LDS tiles alternate, so a plane costs one
+// barrier.  Stores: interior cells of coarse planes [cbegin, cend).
+template <typename T>
+__global__ void __launch_bounds__(kMgThreads)
+    restrict_source_kernel(const T* __restrict__ g, T* __restrict__ gc, Geom gf, Geom gcs, int64_t cbegin, int64_t cend) {
+    __shared__ T sg[2][kMgRH * kMgRW];
+    const int tid = int(threadIdx.x);
+    const int64_t X0 = int64_t(blockIdx.x) * kMgTX, Y0 = int64_t(blockIdx.y) * kMgTY;
+    const int64_t Z0 = cbegin + int64_t(blockIdx.z) * kMgZRun;
+    const int64_t Z1 = Z0 + kMgZRun < cend ? Z0 + kMgZRun : cend;
+    // tile-local (tx, ty) is fine cell (2 X0 + tx, 2 Y0 + ty)
+    int64_t off[kSrcCells];
+    bool ok[kSrcCells];  // an interior fine cell: loaded
+#pragma unroll
+    for (int k = 0; k < kSrcCells; ++k) {
+        const int i = tid + k * kMgThreads;
+        const int ty = i / kMgRW, tx = i - ty * kMgRW;
+        const int64_t fx = 2 * X0 + tx, fy = 2 * Y0 + ty;
+        ok[k] = i < kMgRW * kMgRH && fx < gf.nx && fy < gf.ny;
+        off[k] = gf.origin + fy * gf.row + fx;
+    }
+    const int cx = tid % kMgTX, cy = tid / kMgTX;
+    const int64_t X = X0 + cx, Y = Y0 + cy;
+    const bool stores = X < gcs.nx && Y < gcs.ny;
+    const int64_t zf0 = 2 * Z0, zf1 = 2 * Z1;  // fine planes zf0 .. zf1, both ends included (zf1 <= nz - 1)
+    T v[kSrcCells];
+#pragma unroll
+    for (int k = 0; k < kSrcCells; ++k) v[k] = ok[k] ? g[off[k] + zf0 * gf.plane] : T(0);
+    T p0 = T(0), p1 = T(0);  // P(2Z), P(2Z + 1) of the coarse plane being gathered
+    for (int64_t z = zf0; z <= zf1; ++z) {
+        const int64_t rel = z - zf0;
+        T* s = sg[rel & 1];
+#pragma unroll
+        for (int k = 0; k < kSrcCells; ++k) {
+            const int i = tid + k * kMgThreads;
+            if (i < kMgRW * kMgRH) s[i] = v[k];
+        }
+        if (z < zf1) {
+#pragma unroll
+            for (int k = 0; k < kSrcCells; ++k) v[k] = ok[k] ? g[off[k] + (z + 1) * gf.plane] : T(0);
+        }
+        __syncthreads();
+        const T* row = s + (2 * cy) * kMgRW + 2 * cx;
+        const T a0 = mg_weigh(row[0], row[1], row[2]);
+        const T a1 = mg_weigh(row[kMgRW], row[kMgRW + 1], row[kMgRW + 2]);
+        const T a2 = mg_weigh(row[2 * kMgRW], row[2 * kMgRW + 1], row[2 * kMgRW + 2]);
+        const T p = mg_weigh(a0, a1, a2);
+        if (rel & 1) {
+            p1 = p;
+        } else {
+            if (rel > 0 && stores) {
+                const int64_t Z = Z0 + rel / 2 - 1;
+                gc[gcs.origin + Z * gcs.plane + Y * gcs.row + X] = T(0.0625) * mg_weigh(p0, p1, p);
+            }
+            p0 = p;
+        }
+    }
+}
+
+constexpr int kInjThreads = 256;
+
+// The shell of the coarse ghost-padded box, one cell per lane: the two ghost planes whole, then per interior
+// plane the two ghost rows whole and the two ghost cells of every interior row.
+inline int64_t shell_cells(const Geom& c) {
+    return 2 * (c.ny + 2) * (c.nx + 2) + c.nz * (2 * (c.nx + 2) + 2 * c.ny);
+}
+
+// Coarse shell cell (X, Y, Z) = fine ghost-shell cell (2X+1, 2Y+1, 2Z+1), into c0 and (if given) c1
+template <typename T>
+__global__ void __launch_bounds__(kInjThreads)
+    inject_ghosts_kernel(const T* __restrict__ u, T* __restrict__ c0, T* __restrict__ c1, Geom gf, Geom gcs, int64_t total) {
+    int64_t t = int64_t(blockIdx.x) * kInjThreads + threadIdx.x;
+    if (t >= total) return;
+    const int64_t W = gcs.nx + 2, area = W * (gcs.ny + 2), ring = 2 * W + 2 * gcs.ny;
+    int64_t X, Y, Z;
+    if (t < 2 * area) {
+        Z = t < area ? -1 : gcs.nz;
+        const int64_t r = t < area ? t : t - area;
+        Y = r / W - 1;
+        X = r % W - 1;
+    } else {
+        t -= 2 * area;
+        Z = t / ring;
+        int64_t r = t % ring;
+        if (r < 2 * W) {
+            Y = r < W ? -1 : gcs.ny;
+            X = (r < W ? r : r - W) - 1;
+        } else {
+            r -= 2 * W;
+            Y = r / 2;
+            X = (r & 1) ? gcs.nx : -1;
+        }
+    }
+    const T v = u[gf.origin + (2 * Z + 1) * gf.plane + (2 * Y + 1) * gf.row + (2 * X + 1)];
+    const int64_t ci = gcs.origin + Z * gcs.plane + Y * gcs.row + X;
+    c0[ci] = v;
+    if (c1) c1[ci] = v;
+}
+
+constexpr int kCubicChunk = 16;  // fine planes per workgroup
+
+// Fine index i along an axis of coarse extent m, in PADDED coarse indices (P = coarse index + 1, 0 .. m + 1):
+// the four nodes P = s .. s + 3 (clamped to m + 1 where m = 1 has only three) and what to make of them.
+// s = clamp(i / 2 - 1, 0, m - 2) never decreases with i, so a march along the axis keeps a sliding window.
+template <typename T>
+struct CubicAx {
+    int64_t s;
+    T w0, w1, w2, w3;  // the cubic's integer weights
+    bool copy;         // odd i: node 1 (hi: node 2) exactly
+    bool lin;          // even i, m = 1: the mean of nodes 0, 1 (hi: 1, 2)
+    bool hi;
+};
+
+template <typename T>
+__device__ __forceinline__ CubicAx<T> cubic_ax(int64_t i, int64_t m) {
+    CubicAx<T> a;
+    const int64_t k = i >> 1, top = m >= 2 ? m - 2 : 0;
+    const int64_t lo = k - 1 > 0 ? k - 1 : 0;
+    a.s = lo < top ? lo : top;
+    a.copy = i & 1;
+    a.lin = !a.copy && m == 1;
+    a.hi = a.copy ? k + 1 - a.s == 2 : k == 1;
+    const bool first = k == 0, last = k == m;
+    a.w0 = first ? T(5) : last ? T(1) : T(-1);
+    a.w1 = first ? T(15) : last ? T(-5) : T(9);
+    a.w2 = first ? T(-5) : last ? T(15) : T(9);
+    a.w3 = first ? T(1) : last ? T(5) : T(-1);
+    return a;
+}
+
+// fl(0.0625 * fl( fl(fl(w0 p0) + fl(w1 p1)) + fl(fl(w2 p2) + fl(w3 p3)) )), or the copy, or the mean: selects,
+// no branch on the arithmetic
+template <typename T>
+__device__ __forceinline__ T cubic_apply(T p0, T p1, T p2, T p3, const CubicAx<T>& a) {
+    const T t0 = a.w0 * p0, t1 = a.w1 * p1, t2 = a.w2 * p2, t3 = a.w3 * p3;
+    const T left = t0 + t1, right = t2 + t3;
+    const T sum = left + right;
+    const T cub = T(0.0625) * sum;
+    const T la = a.hi ? p1 : p0, lb = a.hi ? p2 : p1;
+    const T pair = la + lb;
+    const T mean = T(0.5) * pair;
+    return a.copy ? lb : a.lin ? mean : cub;
+}
+
+// u = the cubic prolongation of e at the interior cells of fine planes [begin, end): prolong_add_kernel's shape
+// (one fine cell per lane, a wave is one row, so the parities of y and z are wave-uniform and an odd y takes
+// one coarse row instead of four).  A lane marches kCubicChunk fine planes upward and keeps the in-plane
+// values of the four coarse planes of its z window in registers; the window moves up by at most one coarse
+// plane per fine plane.  e comes from cache, u is written once and never read.
+template <typename T>
+__global__ void __launch_bounds__(kPX * kPY)
+    prolong_cubic_kernel(const T* __restrict__ e, T* __restrict__ u, Geom gcs, Geom gf, int64_t begin, int64_t end) {
+    const int64_t x = int64_t(blockIdx.x) * kPX + threadIdx.x;
+    const int64_t y = int64_t(blockIdx.y) * kPY + threadIdx.y;
+    if (x >= gf.nx || y >= gf.ny) return;
+    const int64_t za = begin + int64_t(blockIdx.z) * kCubicChunk;
+    const int64_t zb = za + kCubicChunk < end ? za + kCubicChunk : end;
+    const CubicAx<T> ax = cubic_ax<T>(x, gcs.nx), ay = cubic_ax<T>(y, gcs.ny);
+    const int64_t px = gcs.nx + 1, py = gcs.ny + 1, pz = gcs.nz + 1;  // the last padded index per axis
+    const T* corner = e + (gcs.origin - gcs.plane - gcs.row - 1);    // padded (0, 0, 0)
+    int64_t xo[4], yo[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        xo[j] = ax.s + j < px ? ax.s + j : px;
+        yo[j] = (ay.s + j < py ? ay.s + j : py) * gcs.row;
+    }
+    auto in_row = [&](const T* r) -> T { return cubic_apply(r[xo[0]], r[xo[1]], r[xo[2]], r[xo[3]], ax); };
+    auto in_plane = [&](int64_t P) -> T {
+        const T* pl = corner + (P < pz ? P : pz) * gcs.plane;
+        if (ay.copy) return in_row(pl + yo[ay.hi ? 2 : 1]);
+        return cubic_apply(in_row(pl + yo[0]), in_row(pl + yo[1]), in_row(pl + yo[2]), in_row(pl + yo[3]), ay);
+    };
+    int64_t cur = cubic_ax<T>(za, gcs.nz).s;
+    T q0 = in_plane(cur), q1 = in_plane(cur + 1), q2 = in_plane(cur + 2), q3 = in_plane(cur + 3);
+    int64_t idx = gf.origin + za * gf.plane + y * gf.row + x;
+    for (int64_t z = za; z < zb; ++z, idx += gf.plane) {
+        const CubicAx<T> az = cubic_ax<T>(z, gcs.nz);
+        if (az.s != cur) {  // one coarse plane up
+            cur = az.s;
+            q0 = q1;
+            q1 = q2;
+            q2 = q3;
+            q3 = in_plane(cur + 3);
+        }
+        u[idx] = cubic_apply(q0, q1, q2, q3, az);
+    }
+}
+
 constexpr int kRnThreads = 256, kRnX = 64, kRnY = kRnThreads / kRnX;
 constexpr int64_t kRnChunkTrips = 16;  // trips per workgroup aimed at ...
 constexpr int kRnMaxChunks = 32;       // ... up to this many chunks per plane
@@ -376,6 +570,56 @@ int launch_prolong(const stencil_layout& lc, const void* e, const stencil_layout
         const int64_t z1 = std::min(end, z0 + kProlongSpan);
         const unsigned gz = unsigned((z1 - z0 + kProlongChunk - 1) / kProlongChunk);
         hipLaunchKernelGGL(prolong_add_kernel<T>, dim3(unsigned(gx), unsigned(gy), gz), dim3(kPX, kPY, 1), 0, s,
+                           static_cast<const T*>(e), static_cast<T*>(u), gcs, gf, z0, z1);
+        STENCIL_LAUNCH_CHECK();
+    }
+    return STENCIL_OK;
+}
+
+constexpr int64_t kCubicSpan = int64_t(65535) * kCubicChunk;  // fine planes per launch
+int64_t cubic_launches(int64_t planes) { return planes <= 0 ? 0 : (planes + kCubicSpan - 1) / kCubicSpan; }
+
+template <typename T>
+int launch_restrict_source(const stencil_layout& lf, const void* g, const stencil_layout& lc, void* gc, int64_t cbegin,
+                           int64_t cend, hipStream_t s) {
+    const Geom gf = geom_of(lf), gcs = geom_of(lc);
+    if (cend <= cbegin || gcs.nx <= 0 || gcs.ny <= 0) return STENCIL_OK;
+    const int64_t gx = (gcs.nx + kMgTX - 1) / kMgTX, gy = (gcs.ny + kMgTY - 1) / kMgTY;
+    if (gy > 65535 || gx > (int64_t(1) << 31) - 1) return set_error(STENCIL_EINVAL, "grid too large for the restriction");
+    for (int64_t z0 = cbegin; z0 < cend; z0 += kRestrictSpan) {
+        const int64_t z1 = std::min(cend, z0 + kRestrictSpan);
+        const unsigned gz = unsigned((z1 - z0 + kMgZRun - 1) / kMgZRun);
+        hipLaunchKernelGGL(restrict_source_kernel<T>, dim3(unsigned(gx), unsigned(gy), gz), dim3(kMgThreads), 0, s,
+                           static_cast<const T*>(g), static_cast<T*>(gc), gf, gcs, z0, z1);
+        STENCIL_LAUNCH_CHECK();
+    }
+    return STENCIL_OK;
+}
+
+// uc1: a second coarse grid that takes the same cells in the same launch, or NULL
+template <typename T>
+int launch_inject(const stencil_layout& lf, const void* u, const stencil_layout& lc, void* uc0, void* uc1, hipStream_t s) {
+    const Geom gf = geom_of(lf), gcs = geom_of(lc);
+    const int64_t total = shell_cells(gcs);
+    const int64_t blocks = (total + kInjThreads - 1) / kInjThreads;
+    if (blocks > (int64_t(1) << 31) - 1) return set_error(STENCIL_EINVAL, "grid too large for the ghost injection");
+    hipLaunchKernelGGL(inject_ghosts_kernel<T>, dim3(unsigned(blocks)), dim3(kInjThreads), 0, s, static_cast<const T*>(u),
+                       static_cast<T*>(uc0), static_cast<T*>(uc1), gf, gcs, total);
+    STENCIL_LAUNCH_CHECK();
+    return STENCIL_OK;
+}
+
+template <typename T>
+int launch_prolong_cubic(const stencil_layout& lc, const void* e, const stencil_layout& lf, void* u, int64_t begin,
+                         int64_t end, hipStream_t s) {
+    const Geom gf = geom_of(lf), gcs = geom_of(lc);
+    if (end <= begin || gf.nx <= 0 || gf.ny <= 0) return STENCIL_OK;
+    const int64_t gx = (gf.nx + kPX - 1) / kPX, gy = (gf.ny + kPY - 1) / kPY;
+    if (gy > 65535 || gx > (int64_t(1) << 31) - 1) return set_error(STENCIL_EINVAL, "grid too large for the prolongation");
+    for (int64_t z0 = begin; z0 < end; z0 += kCubicSpan) {
+        const int64_t z1 = std::min(end, z0 + kCubicSpan);
+        const unsigned gz = unsigned((z1 - z0 + kCubicChunk - 1) / kCubicChunk);
+        hipLaunchKernelGGL(prolong_cubic_kernel<T>, dim3(unsigned(gx), unsigned(gy), gz), dim3(kPX, kPY, 1), 0, s,
                            static_cast<const T*>(e), static_cast<T*>(u), gcs, gf, z0, z1);
         STENCIL_LAUNCH_CHECK();
     }
@@ -565,6 +809,80 @@ int mg_cycle(stencil_mg* mg, size_t level, const stencil_mg_params& p, void* str
     if (int rc = mg_cycle(mg, level + 1, p, stream)) return rc;
     if (int rc = mg_prolong(c.lay, c.field[c.cur], v.lay, v.field[v.cur], 0, v.lay.prob.nz, s)) return rc;
     return mg_smooth(v, p.post, p, stream);
+}
+
+int mg_restrict_source(const stencil_layout& lf, const void* g, const stencil_layout& lc, void* gc, int64_t cbegin,
+                       int64_t cend, hipStream_t s) {
+    return lf.prob.dtype == STENCIL_F32 ? launch_restrict_source<float>(lf, g, lc, gc, cbegin, cend, s)
+                                        : launch_restrict_source<double>(lf, g, lc, gc, cbegin, cend, s);
+}
+
+int mg_inject(const stencil_layout& lf, const void* u, const stencil_layout& lc, void* uc0, void* uc1, hipStream_t s) {
+    return lf.prob.dtype == STENCIL_F32 ? launch_inject<float>(lf, u, lc, uc0, uc1, s)
+                                        : launch_inject<double>(lf, u, lc, uc0, uc1, s);
+}
+
+int mg_prolong_cubic(const stencil_layout& lc, const void* e, const stencil_layout& lf, void* u, int64_t begin, int64_t end,
+                     hipStream_t s) {
+    return lf.prob.dtype == STENCIL_F32 ? launch_prolong_cubic<float>(lc, e, lf, u, begin, end, s)
+                                        : launch_prolong_cubic<double>(lc, e, lf, u, begin, end, s);
+}
+
+// Both field grids of a level to zero, ghost cells included
+int mg_zero_fields(stencil_mg::Level& v, hipStream_t s) {
+    STENCIL_HIP_CHECK(hipMemsetAsync(v.field[0], 0, size_t(v.lay.bytes), s));
+    STENCIL_HIP_CHECK(hipMemsetAsync(v.field[1], 0, size_t(v.lay.bytes), s));
+    return STENCIL_OK;
+}
+
+// The full multigrid pass (include/stencil_hip.h "Full multigrid")
+int mg_fmg(stencil_mg* mg, const stencil_mg_params& p, uint32_t cycles, void* stream) {
+    hipStream_t s = as_stream(stream);
+    const size_t L = mg->lv.size();
+    // 1. the coarse problems: sources, and the Dirichlet data in both field grids
+    for (size_t l = 0; l + 1 < L; ++l) {
+        stencil_mg::Level &f = mg->lv[l], &c = mg->lv[l + 1];
+        if (int rc = mg_restrict_source(f.lay, f.src, c.lay, c.src, 0, c.lay.prob.nz, s)) return rc;
+        if (int rc = mg_zero_fields(c, s)) return rc;
+        if (int rc = mg_inject(f.lay, f.field[f.cur], c.lay, c.field[0], c.field[1], s)) return rc;
+    }
+    // 2. the coarsest level from a zero interior
+    stencil_mg::Level& last = mg->lv[L - 1];
+    if (L == 1) {  // the caller's ghost cells stay: the interior alone is zeroed, plane by plane
+        const stencil_layout& lay = last.lay;
+        const size_t es = lay.prob.dtype == STENCIL_F32 ? 4 : 8;
+        char* base = static_cast<char*>(last.field[last.cur]) + size_t(lay.origin) * es;
+        for (int64_t z = 0; z < lay.prob.nz; ++z)
+            STENCIL_HIP_CHECK(hipMemset2DAsync(base + size_t(z * lay.plane) * es, size_t(lay.row) * es, 0,
+                                               size_t(lay.prob.nx) * es, size_t(lay.prob.ny), s));
+    }
+    if (int rc = mg_smooth(last, p.coarse_sweeps, p, stream)) return rc;
+    // 3. upward: the cubic prolongation as the starting guess, then `cycles` V-cycles from that level.  The
+    // coarse level goes back to zero in BOTH grids first: mg_cycle zeroes field[cur] alone and relies on the
+    // other grid's ghost cells being zero, which the injection of step 1 broke.
+    for (size_t l = L - 1; l-- > 0;) {
+        stencil_mg::Level &f = mg->lv[l], &c = mg->lv[l + 1];
+        if (int rc = mg_prolong_cubic(c.lay, c.field[c.cur], f.lay, f.field[f.cur], 0, f.lay.prob.nz, s)) return rc;
+        if (int rc = mg_zero_fields(c, s)) return rc;
+        for (uint32_t i = 0; i < cycles; ++i)
+            if (int rc = mg_cycle(mg, l, p, stream)) return rc;
+    }
+    return STENCIL_OK;
+}
+
+// The kernel launches of one V-cycle started at level `from` (stencil_mg_plan's count for from = 0)
+int cycle_launches(const std::vector<stencil_layout>& lays, size_t from, const stencil_mg_params& p, int64_t* total) {
+    for (size_t i = from; i < lays.size(); ++i) {
+        const bool coarsest = i + 1 == lays.size();
+        const uint32_t runs[2] = {coarsest ? p.coarse_sweeps : p.pre, coarsest ? 0u : p.post};
+        for (uint32_t sweeps : runs) {
+            int64_t n = 0;
+            if (int rc = stencil_relax_plan(&lays[i], sweeps, &n, nullptr)) return rc;
+            *total += n;
+        }
+        if (!coarsest) *total += restrict_launches(lays[i + 1].prob.nz) + prolong_launches(lays[i].prob.nz);
+    }
+    return STENCIL_OK;
 }
 
 void mg_release(stencil_mg* mg) {
@@ -786,15 +1104,69 @@ int stencil_mg_plan(const stencil_problem* fine, int32_t levels, const stencil_m
     if (int rc = mg_levels(fine, levels, &lays)) return rc;
     if (int rc = check_mg_params(params)) return rc;
     int64_t total = 0;
-    for (size_t i = 0; i < lays.size(); ++i) {
-        const bool coarsest = i + 1 == lays.size();
-        const uint32_t runs[2] = {coarsest ? params->coarse_sweeps : params->pre, coarsest ? 0u : params->post};
-        for (uint32_t sweeps : runs) {
-            int64_t n = 0;
-            if (int rc = stencil_relax_plan(&lays[i], sweeps, &n, nullptr)) return rc;
-            total += n;
-        }
-        if (!coarsest) total += restrict_launches(lays[i + 1].prob.nz) + prolong_launches(lays[i].prob.nz);
+    if (int rc = cycle_launches(lays, 0, *params, &total)) return rc;
+    if (launches) *launches = total;
+    if (levels_out) *levels_out = int32_t(lays.size());
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_restrict_source(const stencil_layout* lf, const void* src, const stencil_layout* lc, void* coarse_src,
+                            int64_t cbegin, int64_t cend, void* stream) {
+    if (int rc = check_mg_pair(lf, lc)) return rc;
+    if (!src || !coarse_src) return set_error(STENCIL_EINVAL, "null grid");
+    if (src == coarse_src) return set_error(STENCIL_EINVAL, "the source and the coarse source must be distinct grids");
+    if (cbegin < 0 || cend > lc->prob.nz || cbegin > cend)
+        return set_error(STENCIL_EINVAL, "coarse plane range [%lld, %lld) out of bounds [0, %lld)", (long long)cbegin,
+                         (long long)cend, (long long)lc->prob.nz);
+    const int rc = mg_restrict_source(*lf, src, *lc, coarse_src, cbegin, cend, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+int stencil_inject_ghosts(const stencil_layout* lf, const void* u, const stencil_layout* lc, void* uc, void* stream) {
+    if (int rc = check_mg_pair(lf, lc)) return rc;
+    if (!u || !uc) return set_error(STENCIL_EINVAL, "null grid");
+    if (u == uc) return set_error(STENCIL_EINVAL, "the fine and the coarse grid must be distinct");
+    const int rc = mg_inject(*lf, u, *lc, uc, nullptr, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+int stencil_prolong_cubic(const stencil_layout* lc, const void* e, const stencil_layout* lf, void* u, int64_t begin,
+                          int64_t end, void* stream) {
+    if (int rc = check_mg_pair(lf, lc)) return rc;
+    if (!e || !u) return set_error(STENCIL_EINVAL, "null grid");
+    if (e == u) return set_error(STENCIL_EINVAL, "the coarse and the fine grid must be distinct");
+    if (begin < 0 || end > lf->prob.nz || begin > end)
+        return set_error(STENCIL_EINVAL, "fine plane range [%lld, %lld) out of bounds [0, %lld)", (long long)begin,
+                         (long long)end, (long long)lf->prob.nz);
+    const int rc = mg_prolong_cubic(*lc, e, *lf, u, begin, end, as_stream(stream));
+    if (rc == STENCIL_OK) clear_error();
+    return rc;
+}
+
+int stencil_mg_fmg(stencil_mg* mg, const stencil_mg_params* params, uint32_t cycles, void* stream) {
+    if (!mg) return set_error(STENCIL_EINVAL, "null hierarchy");
+    if (int rc = check_mg_params(params)) return rc;
+    if (int rc = mg_fmg(mg, *params, cycles, stream)) return rc;
+    clear_error();
+    return STENCIL_OK;
+}
+
+int stencil_mg_fmg_plan(const stencil_problem* fine, int32_t levels, const stencil_mg_params* params, uint32_t cycles,
+                        int64_t* launches, int32_t* levels_out) {
+    std::vector<stencil_layout> lays;
+    if (int rc = mg_levels(fine, levels, &lays)) return rc;
+    if (int rc = check_mg_params(params)) return rc;
+    int64_t total = 0, n = 0;
+    if (int rc = stencil_relax_plan(&lays.back(), params->coarse_sweeps, &n, nullptr)) return rc;
+    total += n;
+    for (size_t l = 0; l + 1 < lays.size(); ++l) {
+        total += restrict_launches(lays[l + 1].prob.nz) + 1 + cubic_launches(lays[l].prob.nz);
+        int64_t one = 0;
+        if (int rc = cycle_launches(lays, l, *params, &one)) return rc;
+        total += int64_t(cycles) * one;
     }
     if (launches) *launches = total;
     if (levels_out) *levels_out = int32_t(lays.size());

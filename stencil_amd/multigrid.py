@@ -1,13 +1,17 @@
 """Geometric multigrid for the 7-point Poisson solve on one GPU (stencil_mg_*,
 stencil_restrict_residual, stencil_prolong_add, stencil_residual_norms:
-include/stencil_hip.h, csrc/kernels_mg.hip).
+include/stencil_hip.h, csrc/kernels_mg.hip), and its full
+multigrid start-up (stencil_mg_fmg, stencil_restrict_source,
+stencil_inject_ghosts, stencil_prolong_cubic: DESIGN.md §5.10).
 
 `PoissonMultigrid` owns a hierarchy of vertex-centred coarsenings -- odd
 extents n >= 3 coarsen to (n - 1) / 2 -- and runs V-cycles whose smoother is
 the relaxed sweep of JacobiEngine.iterate_relax.  The module functions
 `coarsen`, `restrict_residual`, `prolong_add` and `residual_norms` run the
-transfer kernels on JacobiEngine grids.  Everything is bitwise defined
-(tests/mg_ref.py states it in numpy).
+transfer kernels on JacobiEngine grids; `restrict_source`, `inject_ghosts` and
+`prolong_cubic` those of the full multigrid pass (`PoissonMultigrid.fmg`).
+Everything is bitwise defined (tests/mg_ref.py and tests/fmg_ref.py state it in
+numpy).
 """
 from __future__ import annotations
 
@@ -72,6 +76,33 @@ def prolong_add(coarse: JacobiEngine, e: torch.Tensor, fine: JacobiEngine, u: to
                                             begin, end, _stream_handle(stream)), "stencil_prolong_add", lib=fine.lib)
 
 
+def restrict_source(fine: JacobiEngine, src: torch.Tensor, coarse: JacobiEngine, coarse_src: torch.Tensor,
+                    cbegin: int = 0, cend: int | None = None, stream=None) -> None:
+    """coarse_src = 4 R(src) on coarse planes [cbegin, cend): the coarse
+    problem's source of the full multigrid pass (stencil_restrict_source)."""
+    cend = int(coarse.prob.nz) if cend is None else cend
+    _lib.check(fine.lib.stencil_restrict_source(ctypes.byref(fine.layout), _ptr(src), ctypes.byref(coarse.layout),
+                                                _ptr(coarse_src), cbegin, cend, _stream_handle(stream)),
+               "stencil_restrict_source", lib=fine.lib)
+
+
+def inject_ghosts(fine: JacobiEngine, u: torch.Tensor, coarse: JacobiEngine, uc: torch.Tensor, stream=None) -> None:
+    """uc's ghost shell (edges and corners included) = the cells of u's ghost
+    shell it sits on: the coarse problem's Dirichlet data (stencil_inject_ghosts)."""
+    _lib.check(fine.lib.stencil_inject_ghosts(ctypes.byref(fine.layout), _ptr(u), ctypes.byref(coarse.layout), _ptr(uc),
+                                              _stream_handle(stream)), "stencil_inject_ghosts", lib=fine.lib)
+
+
+def prolong_cubic(coarse: JacobiEngine, e: torch.Tensor, fine: JacobiEngine, u: torch.Tensor, begin: int = 0,
+                  end: int | None = None, stream=None) -> None:
+    """u = the cubic prolongation of e on fine planes [begin, end) -- a set,
+    not an add (stencil_prolong_cubic); e's ghost ring is read, edges and
+    corners included."""
+    end = int(fine.prob.nz) if end is None else end
+    _lib.check(fine.lib.stencil_prolong_cubic(ctypes.byref(coarse.layout), _ptr(e), ctypes.byref(fine.layout), _ptr(u),
+                                              begin, end, _stream_handle(stream)), "stencil_prolong_cubic", lib=fine.lib)
+
+
 def _residual_norms(lib, layout, u_ptr, src_ptr, begin, end, stream):
     n = max(0, end - begin)
     max_abs, sum_sq = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
@@ -113,6 +144,19 @@ def mg_plan(spec: StencilSpec, nx: int, ny: int, nz: int, levels: int = 0, pre: 
     launches, nlev = ctypes.c_int64(0), ctypes.c_int32(0)
     _lib.check(lib.stencil_mg_plan(ctypes.byref(prob), levels, ctypes.byref(par), ctypes.byref(launches),
                                    ctypes.byref(nlev)), "stencil_mg_plan", lib=lib)
+    return {"launches": int(launches.value), "levels": int(nlev.value)}
+
+
+def fmg_plan(spec: StencilSpec, nx: int, ny: int, nz: int, levels: int = 0, cycles: int = 2, pre: int = 2, post: int = 2,
+             coarse_sweeps: int = 8, omegas=DEFAULT_OMEGAS, lib=None) -> dict:
+    """One full multigrid pass as kernel launches (memsets not counted), and
+    the level count (stencil_mg_fmg_plan; host only, no device)."""
+    lib = lib if lib is not None else _lib.load()
+    prob = spec.problem(nx, ny, nz)
+    par, _keep = _params(pre, post, coarse_sweeps, omegas)
+    launches, nlev = ctypes.c_int64(0), ctypes.c_int32(0)
+    _lib.check(lib.stencil_mg_fmg_plan(ctypes.byref(prob), levels, ctypes.byref(par), cycles, ctypes.byref(launches),
+                                       ctypes.byref(nlev)), "stencil_mg_fmg_plan", lib=lib)
     return {"launches": int(launches.value), "levels": int(nlev.value)}
 
 
@@ -251,6 +295,24 @@ class PoissonMultigrid:
             for _ in range(cycles):
                 _lib.check(self.lib.stencil_mg_vcycle(self.mg, ctypes.byref(par), _stream_handle(stream)),
                            "stencil_mg_vcycle", lib=self.lib)
+
+    def fmg(self, cycles: int = 2, pre: int = 2, post: int = 2, coarse_sweeps: int = 8, omegas=DEFAULT_OMEGAS,
+            stream=None) -> None:
+        """One full multigrid pass (stencil_mg_fmg): the coarsest problem
+        solved, then per level upward the cubic prolongation as the starting
+        guess and `cycles` V(pre, post) cycles.  The fine field's interior is
+        ignored and overwritten; its ghost shell is the Dirichlet data, EDGES
+        AND CORNERS INCLUDED (the prolongation reads them)."""
+        par, _keep = _params(pre, post, coarse_sweeps, omegas)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.stencil_mg_fmg(self.mg, ctypes.byref(par), cycles, _stream_handle(stream)),
+                       "stencil_mg_fmg", lib=self.lib)
+
+    def fmg_plan(self, cycles: int = 2, pre: int = 2, post: int = 2, coarse_sweeps: int = 8,
+                 omegas=DEFAULT_OMEGAS) -> dict:
+        """One full multigrid pass as kernel launches (stencil_mg_fmg_plan)."""
+        return fmg_plan(self.spec, *self.shape, levels=self.levels, cycles=cycles, pre=pre, post=post,
+                        coarse_sweeps=coarse_sweeps, omegas=omegas, lib=self.lib)
 
     def solve(self, tol: float, max_cycles: int, check_every: int = 1, norm: str = "max", pre: int = 2, post: int = 2,
               coarse_sweeps: int = 8, omegas=DEFAULT_OMEGAS, stream=None, timed: bool = False) -> UntilResult:
